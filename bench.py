@@ -16,10 +16,24 @@ Metric (BASELINE.json): "MPI_Allreduce busBW GB/s (256 MiB fp32 SUM,
   collective library is not available the N>1 run reports independent
   Reduce_local replicas instead and says so in config.workload.
 
-The JSON line also carries `roofline` (the dominant kernel's achieved
-bytes/launch / its HIP-event-timed average duration vs the 8 TB/s HBM
-peak) and `cpu_baseline` (the CPU oracle's restatement of the reference's
-fp32 SUM loop, timed on one host core on a bounded sample).
+A plain run (`--gpus N --steps K --warmup W`) sets up, warms up, times the
+K steps and prints one JSON line: `metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` (milliseconds per timed step),
+the configuration and, at N = 1, `roofline` (the dominant kernel's
+achieved bytes/launch / the HIP-event-timed average duration of the timed
+launches vs the 8 TB/s HBM peak).
+
+`--dump-outputs DIR` writes what the timed path left in the caller's
+buffers after its last timed step as DIR/<name>.npy (float32; a fixed,
+seeded sample of the elements, see dump_sample).  The inputs are seeded, so
+two builds run with the same arguments can be compared output for output.
+
+`--full` adds everything else after the headline: the parity checks against
+the oracle, `cpu_baseline` (the CPU oracle's restatement of the reference's
+fp32 SUM loop, timed on one host core on a bounded sample) and the other CPU
+proxies, the size-1 allreduce, pack / unpack, the op call cost, and at N > 1
+the profiled pass, the data-path A/B, the CFG-D sweep, the CFG-E lines and
+the RCCL leg.
 """
 from __future__ import annotations
 
@@ -285,7 +299,29 @@ def cpu_baseline_allreduce(ranks=8, nbytes=256 << 20, iters=10):
         return {"error": repr(e)}
 
 
-def bench_reduce_local(torch, mx, steps, warmup, nbytes=1 << 30):
+DUMP_SEED = 0xD0C5          # the element sample of --dump-outputs
+DUMP_SAMPLE = 1 << 22       # elements per dumped array (16 MiB of float32)
+
+
+def dump_sample(torch, t, dump_dir, name, nsample=DUMP_SAMPLE):
+    """--dump-outputs: write the fp32 device tensor `t` to dump_dir/name.npy.
+    A tensor of more than `nsample` elements is written as a fixed sample:
+    its first and last nsample/4 elements and nsample/2 elements at sorted
+    indices drawn once from a seeded host generator (the same indices in
+    every run and every build for a given length)."""
+    import numpy as np
+    os.makedirs(dump_dir, exist_ok=True)
+    n = t.numel()
+    if n > nsample:
+        q = nsample // 4
+        mid = np.sort(np.random.default_rng(DUMP_SEED).integers(q, n - q, nsample - 2 * q))
+        idx = np.concatenate([np.arange(q), mid, np.arange(n - q, n)]).astype(np.int64)
+        t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+    torch.cuda.synchronize()
+    np.save(os.path.join(dump_dir, name + ".npy"), t.reshape(-1).cpu().numpy().astype(np.float32, copy=False))
+
+
+def bench_reduce_local(torch, mx, steps, warmup, nbytes=1 << 30, full=True, dump_dir=None):
     n = nbytes // 4
     g = torch.Generator(device="cuda").manual_seed(0x5EEDC0DE)
     # the three 1 GiB buffers are allocated first, as whole fresh segments,
@@ -314,6 +350,11 @@ def bench_reduce_local(torch, mx, steps, warmup, nbytes=1 << 30):
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     kms = [e0.elapsed_time(e1) / steps] * steps      # average launch duration incl. the kernel boundaries
+    if dump_dir:
+        # the inout buffer as the caller holds it after the last timed step
+        dump_sample(torch, b, dump_dir, "reduce_local_inout")
+    if not full:
+        return wall, kms, 3.0 * n * 4, None
     # parity, outside the timed region: one more call on a fresh copy of b0
     # against the same IEEE fp32 sum computed by a torch kernel (a 2-operand
     # fp32 add has one correctly rounded result, so the check is bit-exact)
@@ -327,10 +368,12 @@ def bench_reduce_local(torch, mx, steps, warmup, nbytes=1 << 30):
     return wall, kms, 3.0 * n * 4, parity
 
 
-def bench_allreduce(torch, mx, dist, rank, world, dev, steps, warmup, nbytes=256 << 20, extras=True):
+def bench_allreduce(torch, mx, dist, rank, world, dev, steps, warmup, nbytes=256 << 20, extras=True, full=True,
+                    dump_dir=None):
     """MPI_Allreduce 256 MiB fp32 SUM per rank through the all-peer path
     (coll/tuned's fixed decision -> segmented-ring fold order).  Returns
-    the result dict fields, or raises if the path is unavailable."""
+    the result dict fields, or raises if the path is unavailable.  Without
+    `full` only the headline is timed."""
     count = nbytes // 4
 
     def ag(b):
@@ -371,6 +414,21 @@ def bench_allreduce(torch, mx, dist, rank, world, dev, steps, warmup, nbytes=256
     t_max = timed("auto", steps)
     algbw = nbytes / (t_max / steps) / 1e9
     busbw = algbw * 2 * (world - 1) / world
+    if dump_dir:
+        # every rank's rbuf after the last timed call (the sample is 1/4 of
+        # the N = 1 one so that eight ranks stay under 64 MB together)
+        dump_sample(torch, out, dump_dir, f"allreduce_rbuf_rank{rank}", DUMP_SAMPLE // 4)
+    headline = {"value": round(busbw, 2), "unit": "GB/s", "ms_per_step": round(t_max / steps * 1e3, 4)}
+    headline_config = {"workload": "MPI_Allreduce fp32 SUM 256 MiB per rank (coll/tuned fixed decision: "
+                                   "segmented-ring fold order), all-peer xGMI",
+                       "count": count, "bytes": nbytes, "algorithm": "auto",
+                       "parallelism": f"allreduce-{world}", "algbw_gbs": round(algbw, 2)}
+    if not full:
+        tuned_now = comm.tuning(nbytes)
+        comm.close()
+        return {**headline, "config": {**headline_config, "autotuned": tuned_now,
+                                       "autotune_calls_before_warmup": tune_calls,
+                                       "busbw_formula": "algbw*2(n-1)/n"}}
     # profiled pass: per-kernel device time of the fused fold (dominant kernel)
     comm.set_profiling(True)
     comm.stats(reset=True)
@@ -441,11 +499,8 @@ def bench_allreduce(torch, mx, dist, rank, world, dev, steps, warmup, nbytes=256
     fold_bytes_call = st["fold_bytes"] / max(1, st["calls"])   # every chunk's fold of one call
     return {
         **par,
-        "value": round(busbw, 2), "unit": "GB/s", "ms_per_step": round(t_max / steps * 1e3, 4),
-        "config": {"workload": "MPI_Allreduce fp32 SUM 256 MiB per rank (coll/tuned fixed decision: "
-                               "segmented-ring fold order), all-peer xGMI",
-                   "count": count, "bytes": nbytes, "algorithm": "auto",
-                   "parallelism": f"allreduce-{world}", "algbw_gbs": round(algbw, 2),
+        **headline,
+        "config": {**headline_config,
                    "data_path_ab": proto_ab,
                    "autotune_calls_before_warmup": tune_calls, "autotuned_paths": tuned,
                    "busbw_formula": "algbw*2(n-1)/n", **extra},
@@ -850,14 +905,23 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step to "
+                         "DIR/<name>.npy (float32, a fixed seeded sample of each buffer)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the parity checks, the CPU baselines, the size-1 allreduce, "
+                         "pack / unpack and the op call cost (N=1), and the profiled pass, data-path A/B, sweep, "
+                         "CFG-E lines and RCCL leg (N>1)")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: seconds of the CPU fp32 SUM baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave the CPU baselines out")
     ap.add_argument("--no-sweep", action="store_true",
-                    help="N>1: skip the CFG-D size sweep and the CFG-E lines (the headline allreduce, its parity "
-                         "check and the data-path A/B still run)")
+                    help="--full, N>1: skip the CFG-D size sweep and the CFG-E lines (the headline allreduce, its "
+                         "parity check and the data-path A/B still run)")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     launched = "WORLD_SIZE" in os.environ
     if not launched and args.gpus > 1:
@@ -890,12 +954,14 @@ def main():
     if world > 1:
         try:
             result.update(bench_allreduce(torch, mx, dist, rank, world, dev, args.steps, args.warmup,
-                                          extras=not args.no_sweep))
+                                          extras=not args.no_sweep, full=args.full,
+                                          dump_dir=args.dump_outputs))
             done = True
         except Exception as e:  # noqa: BLE001 - reported in the JSON line
             result["allreduce_error"] = repr(e)
         rccl_ref = result.pop("_rccl_ref", (None, None))
-        if done and torch.cuda.device_count() >= world and os.environ.get("MX_BENCH_RCCL", "1") != "0":
+        rccl = done and args.full
+        if rccl and torch.cuda.device_count() >= world and os.environ.get("MX_BENCH_RCCL", "1") != "0":
             # RCCL over xGMI beside the default path.  A watchdog ends the
             # ranks with the line printed if RCCL's bootstrap or a collective
             # never returns, so the headline is not lost with it.
@@ -914,7 +980,7 @@ def main():
             except Exception as e:  # noqa: BLE001 - reported in the JSON line
                 result["rccl_error"] = repr(e)
             wd.cancel()
-        elif done:
+        elif rccl:
             result["rccl_busbw_gbs"] = None
             result["rccl_parity"] = f"not run: {torch.cuda.device_count()} GPU(s) for {world} ranks " \
                                     "(RCCL needs one GPU per rank)"
@@ -922,7 +988,8 @@ def main():
         torch.cuda.synchronize()
         if dist is not None:
             dist.barrier()
-        wall, kms, algo_bytes, parity = bench_reduce_local(torch, mx, args.steps, args.warmup)
+        wall, kms, algo_bytes, parity = bench_reduce_local(torch, mx, args.steps, args.warmup, full=args.full,
+                                                           dump_dir=args.dump_outputs if rank == 0 else None)
         torch.cuda.synchronize()
         t_max = wall
         if dist is not None:
@@ -945,11 +1012,16 @@ def main():
                          "kernel": "k_reduce2<float, mx::OpSum, true> (non-temporal instance at >= 384 MiB footprint)",
                          "algorithmic_bytes_per_launch": algo_bytes,
                          "avg_kernel_ms": round(avg_kernel_ms, 4)},
-            "parity": parity,
-            "parity_check": {"what": "one more mx_reduce2 fp32 SUM of the 1 GiB inputs after the timed region, "
-                                     "bit-compared with the same sum by a torch kernel (IEEE fp32 add)"},
         })
-    if rank == 0 and world == 1:
+        if args.full:
+            result.update({
+                "parity": parity,
+                "parity_check": {"what": "one more mx_reduce2 fp32 SUM of the 1 GiB inputs after the timed region, "
+                                         "bit-compared with the same sum by a torch kernel (IEEE fp32 add)"},
+            })
+    # everything below is beside the headline: --full only
+    cpu_legs = args.full and not args.no_cpu_baseline
+    if args.full and rank == 0 and world == 1:
         try:
             result["allreduce_n1"] = allreduce_n1(torch, mx)
         except Exception as e:  # noqa: BLE001 - reported in the JSON line
@@ -963,12 +1035,12 @@ def main():
             result["op_reduce_call_us"] = op_reduce_call_cost(torch, mx)
         except Exception as e:  # noqa: BLE001 - reported in the JSON line
             result["op_reduce_call_us"] = {"error": repr(e)}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and cpu_legs:
         result["cpu_baseline"] = cpu_baseline_reduce_local(args.cpu_seconds)
         result["cpu_baseline_pack"] = {k: result["pack_unpack"].get(k) for k in ("cpu", "types")} \
             if "types" in result.get("pack_unpack", {}) else result.get("pack_unpack")
         result["cpu_baseline_allreduce"] = cpu_baseline_allreduce()
-    elif world > 1 and done and not args.no_cpu_baseline:
+    elif world > 1 and done and cpu_legs:
         # the host allreduce of the same shape (world ranks, 256 MiB fp32
         # SUM) on the box's own cores, beside the GPU number
         if rank == 0:

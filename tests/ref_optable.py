@@ -1,5 +1,9 @@
-"""Reads the (op, type) availability pattern straight from the text of the
-reference's ompi/mca/op/base/op_base_functions.c (TEST INFRASTRUCTURE).
+"""The (op, type) availability pattern of the reference's
+ompi/mca/op/base/op_base_functions.c (TEST INFRASTRUCTURE).
+
+pattern() returns it from tests/golden/ref_optable.json, the list of (op,
+type) names that oracle/record_reference_facts.py recorded with
+pattern_from_source() below, so the tests need no reference tree.
 
 The kernel tables (ompi_op_base_functions :1485-1569,
 ompi_op_base_3buff_functions :1572-1655) are designated initialisers built
@@ -11,10 +15,12 @@ blocks around them under a given configuration, and the table rows -- a
 reading of the reference, nothing of it is compiled.  A slot is available
 when its initialiser expands to a function name rather than NULL.
 """
+import json
 import os
 import re
 
-SRC = "/root/reference/ompi/mca/op/base/op_base_functions.c"
+SRC = "ompi/mca/op/base/op_base_functions.c"      # in a reference tree
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_optable.json")
 
 OPS = ["NULL", "MAX", "MIN", "SUM", "PROD", "LAND", "BAND", "LOR", "BOR", "LXOR", "BXOR", "MAXLOC", "MINLOC",
        "REPLACE", "NO_OP"]
@@ -85,9 +91,26 @@ def _entries(group_call, macros):
     return out
 
 
+def _key(fortran, three):
+    return ("with_fortran" if fortran else "c_only") + ("/3buff" if three else "/2buff")
+
+
 def pattern(fortran, three=False):
     """{(op name, type slot name)} with a kernel in the reference table."""
-    text = open(SRC).read()
+    with open(GOLDEN) as f:
+        return {tuple(p) for p in json.load(f)["patterns"][_key(fortran, three)]}
+
+
+def record(ref):
+    """The content of GOLDEN, read from the reference tree at `ref`."""
+    src = os.path.join(ref, SRC)
+    return {"source": SRC,
+            "patterns": {_key(f, t): sorted(pattern_from_source(src, f, t)) for f in (0, 1) for t in (False, True)}}
+
+
+def pattern_from_source(src, fortran, three=False):
+    """The same set, expanded from the text of op_base_functions.c at `src`."""
+    text = open(src).read()
     macros = _macros(text, config(fortran))
     table = "ompi_op_base_3buff_functions" if three else "ompi_op_base_functions"
     m = re.search(r"ompi_op_base_(?:3buff_)?handler_fn_t\s+" + table + r"\s*\[[^\]]*\]\s*\[[^\]]*\]\s*=\s*\{", text)
@@ -105,7 +128,3 @@ def pattern(fortran, three=False):
                 if v:
                     pat.add((op, t))
     return pat
-
-
-def available():
-    return os.path.exists(SRC)

@@ -24,7 +24,6 @@ import mxompi
 import oracle_lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
 
 
 # the op / coll / mca_base layouts are checked member by member against the

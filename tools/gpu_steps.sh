@@ -6,7 +6,7 @@
 #   bash tools/gpu_steps.sh r6a \
 #     'suite|900|python -u -m pytest -x -q --timeout 240 --timeout-method thread tests -m gpu' \
 #     'smoke|300|python -c "import __graft_entry__ as g; g.smoke()"' \
-#     'bench|400|python bench.py'
+#     'bench|400|python bench.py --full'
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-.}"
 export TMPDIR=/tmp HSA_ENABLE_IPC_MODE_LEGACY=0 PYTHONUNBUFFERED=1
