@@ -177,7 +177,7 @@ def test_butterfly_reduce_scatter_is_the_recursive_doubling_tree(n):
     recursive doubling allreduce gives it (coll_base_allreduce.c:130-274):
     masks ascending, the higher virtual rank's partial the target, the odd
     rank the target of the non-power-of-two leaf.  This is the identity the
-    device fold program relies on (mx_coll.hip reduce_scatter_segments)."""
+    device fold program relies on (mx_plan.hip reduce_scatter_segments)."""
     L = _L()
     rng = np.random.default_rng(n)
     rcounts = [int(x) for x in rng.integers(0, 4, n)]

@@ -1,0 +1,23 @@
+"""CPU: the reduction-order planning unit (csrc/mx_plan.hip) compiles with the
+host compiler alone -- no HIP library -- and, under AddressSanitizer and
+UBSan, every order it plans for 2..MX_MAX_RANKS ranks keeps the invariants
+the fold kernels assume (tests/native/plan_check.cpp)."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="no host C++ compiler")
+def test_plan_invariants_under_host_sanitizers(tmp_path):
+    exe = tmp_path / "plan_check"
+    csrc = os.path.join(ROOT, "zhpe-ompi_amd", "csrc")
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover=all", "-I", csrc,
+                    os.path.join(ROOT, "tests", "native", "plan_check.cpp"),
+                    "-x", "c++", os.path.join(csrc, "mx_plan.hip"), "-o", str(exe)], check=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-4000:]

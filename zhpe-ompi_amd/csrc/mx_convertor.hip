@@ -30,6 +30,7 @@
 #include "mx_internal.h"
 #include "mx_mem.hpp"
 #include "../../include/mx_convertor.h"
+#include "mx_env.hpp"
 
 namespace mx {
 
@@ -2071,13 +2072,7 @@ static void cut_pieces(const mx_ddt *d, int al, std::vector<DPiece> &v) {
 // MX_CONV_BMAP_INST=0: the byte-map PACK's tiles of non-monotonic layouts
 // stay multiples of 256 stream bytes instead of whole instances (A/B switch;
 // read at datatype creation)
-static bool conv_bmap_inst_tiles() {
-  static const int on = [] {
-    const char *e = getenv("MX_CONV_BMAP_INST");
-    return (e && *e == '0') ? 0 : 1;
-  }();
-  return on != 0;
-}
+static bool conv_bmap_inst_tiles() { static const bool v = env_default_on("MX_CONV_BMAP_INST"); return v; }
 
 static void build_bmap(mx_ddt *d) {
   const int64_t ext = d->ub - d->lb;
@@ -2227,20 +2222,8 @@ static int conv_blk_ng(bool pack) {
 }
 // MX_CONV_BLK_SPAN=0 keeps PACK of monotonic layouts on the granule
 // kernel instead of the span-staged one (A/B switch).
-static bool conv_blk_span() {
-  static const int on = [] {
-    const char *e = getenv("MX_CONV_BLK_SPAN");
-    return (e && *e == '0') ? 0 : 1;
-  }();
-  return on != 0;
-}
-static int conv_blk_w4() {
-  static const int w = [] {
-    const char *e = getenv("MX_CONV_BLK_W4");
-    return (e && *e == '0') ? 0 : 1;
-  }();
-  return w;
-}
+static bool conv_blk_span() { static const bool v = env_default_on("MX_CONV_BLK_SPAN"); return v; }
+static int conv_blk_w4() { static const int v = env_default_on("MX_CONV_BLK_W4"); return v; }
 
 // The block table of k_convert_blk (caller holds d->mu): the instance's
 // contiguous user blocks in stream order (touching blocks merged), tfirst[k]
@@ -2486,63 +2469,27 @@ extern "C" int mx_ddt_span(const mx_ddt_t *d, size_t count, int64_t *lo, int64_t
 
 // MX_CONV_VEC=0 sends single-run layouts to the general kernels instead
 // (A/B measurement switch; results are identical).
-static bool conv_vec_enabled() {
-  static const int on = [] {
-    const char *e = getenv("MX_CONV_VEC");
-    return (e && *e == '0') ? 0 : 1;
-  }();
-  return on != 0;
-}
+static bool conv_vec_enabled() { static const bool v = env_default_on("MX_CONV_VEC"); return v; }
 
 // MX_CONV_PIPE=0 sends PACK to the one-tile-per-workgroup kernel instead
 // of the pipelined one (A/B switch; results are identical).
-static bool conv_pipe_enabled() {
-  static const int on = [] {
-    const char *e = getenv("MX_CONV_PIPE");
-    return (e && *e == '0') ? 0 : 1;
-  }();
-  return on != 0;
-}
+static bool conv_pipe_enabled() { static const bool v = env_default_on("MX_CONV_PIPE"); return v; }
 
 // MX_CONV_BMAP=0 keeps small irregular instances on the run-walking tile
 // kernels (A/B switch; results are identical).
-static bool conv_bmap_enabled() {
-  static const int on = [] {
-    const char *e = getenv("MX_CONV_BMAP");
-    return (e && *e == '0') ? 0 : 1;
-  }();
-  return on != 0;
-}
+static bool conv_bmap_enabled() { static const bool v = env_default_on("MX_CONV_BMAP"); return v; }
 
 // MX_CONV_BMAP_PACK=0 sends PACK of small dense instances to the piece
 // kernel instead of the byte-map kernel (A/B switch).
-static bool conv_bmap_pack_enabled() {
-  static const int on = [] {
-    const char *e = getenv("MX_CONV_BMAP_PACK");
-    return (e && *e == '0') ? 0 : 1;
-  }();
-  return on != 0;
-}
+static bool conv_bmap_pack_enabled() { static const bool v = env_default_on("MX_CONV_BMAP_PACK"); return v; }
 
 // MX_CONV_PPACK=0 keeps PACK of layouts the byte map does not take on the
 // run-walking kernels instead of the piece kernel (A/B switch).
-static bool conv_ppack_enabled() {
-  static const int on = [] {
-    const char *e = getenv("MX_CONV_PPACK");
-    return (e && *e == '0') ? 0 : 1;
-  }();
-  return on != 0;
-}
+static bool conv_ppack_enabled() { static const bool v = env_default_on("MX_CONV_PPACK"); return v; }
 
 // MX_CONV_BMAP_DW=0 gives each lane of the byte-map PACK kernel 16 packed
 // bytes (one 16-byte store) instead of one dword per step (A/B switch).
-static bool conv_bmap_dw() {
-  static const int on = [] {
-    const char *e = getenv("MX_CONV_BMAP_DW");
-    return (e && *e == '0') ? 0 : 1;
-  }();
-  return on != 0;
-}
+static bool conv_bmap_dw() { static const bool v = env_default_on("MX_CONV_BMAP_DW"); return v; }
 
 // MX_CONV_BLK: 0 keeps every layout off the BLOCK kernels, 1 (default)
 // sends instances without a byte map (> kBmapMaxS packed bytes) to them,
@@ -2559,13 +2506,7 @@ static int conv_blk_mode() {
 
 // MX_CONV_BMAP_PIPE=0 runs the byte-map PACK kernel without the span
 // prefetch of the next tile (A/B switch; results are identical).
-static bool conv_bmap_pipe() {
-  static const int on = [] {
-    const char *e = getenv("MX_CONV_BMAP_PIPE");
-    return (e && *e == '0') ? 0 : 1;
-  }();
-  return on != 0;
-}
+static bool conv_bmap_pipe() { static const bool v = env_default_on("MX_CONV_BMAP_PIPE"); return v; }
 
 // MX_CONV_BMAP_ALIGN=16|128: the byte-map PACK stages a tile's user span
 // from its first 16-byte granule or from the start of that granule's
@@ -2580,90 +2521,42 @@ static uint64_t conv_bmap_align() {
 
 // MX_CONV_BMAP_QUAD=0 stages the byte-map PACK's map as one row also where
 // S % 4 != 0 (A/B switch; results identical)
-static bool conv_bmap_quad() {
-  static const int on = [] {
-    const char *e = getenv("MX_CONV_BMAP_QUAD");
-    return (e && *e == '0') ? 0 : 1;
-  }();
-  return on != 0;
-}
+static bool conv_bmap_quad() { static const bool v = env_default_on("MX_CONV_BMAP_QUAD"); return v; }
 
 // MX_CONV_BMAP_CW=0: the byte-map PACK reads every packed byte on its own
 // also where whole waves of packed dwords are user-contiguous (A/B switch)
-static bool conv_bmap_cw() {
-  static const int on = [] {
-    const char *e = getenv("MX_CONV_BMAP_CW");
-    return (e && *e == '0') ? 0 : 1;
-  }();
-  return on != 0;
-}
+static bool conv_bmap_cw() { static const bool v = env_default_on("MX_CONV_BMAP_CW"); return v; }
 
 // MX_CONV_BMAP_NT=0: the byte-map PACK reads the user span and writes the
 // packed stream with ordinary accesses instead of non-temporal ones (A/B
 // switch).  The span is staged with one coalesced 16-byte load per lane, the
 // pattern whose floor is 1.23x faster non-temporal at 256 MiB
 // (tools/pack_floor_probe split-nt vs split-plain, profiles/r05/pack_floor_r5j.txt)
-static bool conv_bmap_nt() {
-  static const int on = [] {
-    const char *e = getenv("MX_CONV_BMAP_NT");
-    return (e && *e == '0') ? 0 : 1;
-  }();
-  return on != 0;
-}
+static bool conv_bmap_nt() { static const bool v = env_default_on("MX_CONV_BMAP_NT"); return v; }
 
 // MX_CONV_VEC_NT=0: the VEC and VEC-span PACK kernels keep ordinary accesses
 // at the streaming sizes too (A/B switch)
-static bool conv_vec_nt() {
-  static const int on = [] {
-    const char *e = getenv("MX_CONV_VEC_NT");
-    return (e && *e == '0') ? 0 : 1;
-  }();
-  return on != 0;
-}
+static bool conv_vec_nt() { static const bool v = env_default_on("MX_CONV_VEC_NT"); return v; }
 
 // MX_CONV_UNPACK_NTLD=1: the UNPACK kernels read the packed stream with
 // non-temporal loads at the streaming sizes (A/B switch, off: -5 % / +5 %
 // on indexed at 256 MiB / 1 GiB, within 1 % elsewhere, profiles/r05/conv_ab_r5y.txt;
 // the unpack is bound by its partial-line stores)
-static bool conv_unpack_ntld() {
-  static const int on = [] {
-    const char *e = getenv("MX_CONV_UNPACK_NTLD");
-    return (e && *e == '1') ? 1 : 0;
-  }();
-  return on != 0;
-}
+static bool conv_unpack_ntld() { static const bool v = env_default_off("MX_CONV_UNPACK_NTLD"); return v; }
 
 // MX_CONV_UNPACK_U32=0: the piece UNPACK kernel's store loop in 64-bit
 // stream coordinates (round 4's form; A/B switch)
-static bool conv_unpack_u32() {
-  static const int on = [] {
-    const char *e = getenv("MX_CONV_UNPACK_U32");
-    return (e && *e == '0') ? 0 : 1;
-  }();
-  return on != 0;
-}
+static bool conv_unpack_u32() { static const bool v = env_default_on("MX_CONV_UNPACK_U32"); return v; }
 
 // MX_CONV_BMAP_WORD=1: the byte-map PACK stages a word map for word-piece
 // layouts (A/B switch, off: indexed 112 -> 137 us at 256 MiB with it, BLACS
 // equal, profiles/r05/conv_r5r.txt -- the gather gets shorter and the tile's
 // span prefetch, which it hid, is waited for instead)
-static bool conv_bmap_word() {
-  static const int on = [] {
-    const char *e = getenv("MX_CONV_BMAP_WORD");
-    return (e && *e == '1') ? 1 : 0;
-  }();
-  return on != 0;
-}
+static bool conv_bmap_word() { static const bool v = env_default_off("MX_CONV_BMAP_WORD"); return v; }
 
 // MX_CONV_BMAP_UNROLL=0: one packed dword per lane per step in the byte-map
 // PACK's gather instead of kBmapU (A/B switch)
-static bool conv_bmap_unroll() {
-  static const int on = [] {
-    const char *e = getenv("MX_CONV_BMAP_UNROLL");
-    return (e && *e == '0') ? 0 : 1;
-  }();
-  return on != 0;
-}
+static bool conv_bmap_unroll() { static const bool v = env_default_on("MX_CONV_BMAP_UNROLL"); return v; }
 
 // MX_CONV_BMAP_SPAN=12288|24576|49152: user span the byte-map PACK stages
 // per tile (A/B switch; the tile's stream bytes follow from it; unset: 24 KiB
@@ -2681,13 +2574,7 @@ static int conv_bmap_span_idx() {
 // MX_CONV_UNPACK_PIPE=1 runs the piece UNPACK kernel with the register
 // prefetch of the next tile's packed range (A/B switch, off: measured
 // slower; results are identical).
-static bool conv_unpack_pipe() {
-  static const int on = [] {
-    const char *e = getenv("MX_CONV_UNPACK_PIPE");
-    return (e && *e == '1') ? 1 : 0;
-  }();
-  return on != 0;
-}
+static bool conv_unpack_pipe() { static const bool v = env_default_off("MX_CONV_UNPACK_PIPE"); return v; }
 
 // The piece UNPACK form: MX_CONV_UNPACK_DIRECT=0 always the LDS-staged tile
 // kernel, =1 always one piece per lane, unset: measured per datatype
@@ -2742,13 +2629,7 @@ static int unpack_piece_form(mx_ddt *dm, uint64_t len, hipEvent_t *ev0, hipEvent
 
 // MX_CONV_VEC_SPAN=0 packs periodic small-block vectors through the VEC
 // kernel instead of k_pack_vec_span (A/B switch; results are identical).
-static bool conv_vec_span() {
-  static const int on = [] {
-    const char *e = getenv("MX_CONV_VEC_SPAN");
-    return (e && *e == '0') ? 0 : 1;
-  }();
-  return on != 0;
-}
+static bool conv_vec_span() { static const bool v = env_default_on("MX_CONV_VEC_SPAN"); return v; }
 
 static int conv_pipe_geom() {
   static const int g = [] {

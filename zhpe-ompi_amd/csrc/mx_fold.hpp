@@ -1,7 +1,7 @@
 // mx_fold.hpp -- device side of the collective fold: the kernels that read
 // the n contributions of a range of elements and evaluate, per element, the
-// reduction tree of a reference algorithm (see mx_coll.hip for the host
-// side).  Three evaluators:
+// reduction tree of a reference algorithm (mx_plan.hip plans the trees;
+// mx_coll.hip launches).  Three evaluators:
 //   k_fold     CHAIN / BUTTERFLY programs in registers (allreduce and
 //              reduce_scatter: the ring / recursive-doubling / Rabenseifner /
 //              recursive-halving trees);
@@ -21,11 +21,10 @@
 #include "mx_dispatch.hpp"
 #include "mx_internal.h"
 #include "mx_mem.hpp"
-#include "../../include/mx_coll.h"
+#include "mx_plan.hpp"
 
 namespace mx {
 
-constexpr int MAXR = MX_MAX_RANKS;
 constexpr int kFB = 256;  // fold / copy block size
 
 // one-shot small-message allreduce: flag layout shared with mx_coll.hip
@@ -35,7 +34,6 @@ constexpr int kFB = 256;  // fold / copy block size
 // ranks); PUSHED and DONE carry the plain generation.
 enum { FLAG_READY = 0, FLAG_PUSHED = 1, FLAG_DONE = 2, NFLAGS = 3 };
 constexpr int OSWG = 64;
-constexpr int OS_MAXSEG = 16;
 
 
 // Poisoned communicator (mx_comm::poison): a peer wait of an earlier kernel
@@ -49,21 +47,7 @@ __device__ __forceinline__ void raise_timeout(int *err, int *poison) {
   if (poison) __hip_atomic_store(poison, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// ---------------------------------------------------------------------------
-// fold programs
-// ---------------------------------------------------------------------------
-enum { PROG_CHAIN = 0, PROG_BFLY = 1 };
-
-struct FoldProg {
-  int kind;
-  int n;           // chain: number of operands; butterfly: p' leaves
-  int D;           // butterfly depth (p' = 1 << D)
-  int acc_first;   // chain: accumulator is the target (first operand)
-  uint32_t pref;   // butterfly: bit s set -> upper half is the target at level s
-  int8_t ord[MAXR];  // chain: source index per step
-  int8_t la[MAXR];   // butterfly leaf slot i: first operand source
-  int8_t lb[MAXR];   //   second operand source, -1 = plain leaf
-};
+// fold programs (FoldProg, the PROG_* kinds) and VM programs (VmProg): mx_plan.hpp
 
 struct FoldArgs {
   const char *src[MAXR];
@@ -580,17 +564,7 @@ int oneshot_launch(OneShotArgs &a, int nwg, hipStream_t s) {
 // scratch or expanded into selects.
 // ---------------------------------------------------------------------------
 constexpr int kVB = 128;         // VM block size
-constexpr int VM_MAXI = 192;     // instructions per program
-constexpr int VM_MAXREG = 40;    // registers (contributions + temporaries)
 constexpr size_t kVmLdsMax = 160 * 1024;   // LDS per CU, all of it available to one workgroup
-// op: VM_COMB / VM_EMIT, optionally guarded by the call's info bit (the
-// root's MPI_IN_PLACE in a rooted reduce): executed only if set / clear
-enum { VM_COMB = 0, VM_EMIT = 1, VM_IF_SET = 4, VM_IF_CLEAR = 8 };
-struct VmIns { int8_t op, d, a, b; };
-struct VmProg {
-  int nsrc, nregs, nins;
-  VmIns ins[VM_MAXI];
-};
 struct VmArgs {
   const char *src[MAXR];
   char *dst[MAXR];

@@ -53,6 +53,7 @@
 
 #include "mx_comm.hpp"
 #include "../../include/mx_convertor.h"
+#include "mx_env.hpp"
 
 namespace mx {
 
@@ -993,13 +994,7 @@ static RxDev g_rx[64];
 static int g_rx_dev[64], g_rx_ndev;
 // MX_P2P_RGET=0: rendezvous messages always stream through the mailbox
 // (round 5's two-copy path); default: single copy from registered buffers
-static bool rget_on() {
-  static const bool on = [] {
-    const char *e = getenv("MX_P2P_RGET");
-    return !(e && *e == '0');
-  }();
-  return on;
-}
+static bool rget_on() { static const bool v = env_default_on("MX_P2P_RGET"); return v; }
 // smallest rendezvous message sent with its descriptor (MX_P2P_RGET_MIN,
 // bytes): below it the mailbox's two copies beat the pull's host round trip
 // (one GPU, profiles/r06/p2p_lat_r6*.txt: 1 MiB 37 vs 52 us, 16 MiB 81 vs 58 us)
@@ -1015,13 +1010,7 @@ static void rx_dev_note(int dev) {   // caller holds g_chan_mu
     if (g_rx_dev[i] == dev) return;
   g_rx_dev[g_rx_ndev++] = dev;
 }
-static bool rx_yield_on() {
-  static const bool on = [] {
-    const char *e = getenv("MX_P2P_YIELD");
-    return !(e && *e == '0');
-  }();
-  return on;
-}
+static bool rx_yield_on() { static const bool v = env_default_on("MX_P2P_YIELD"); return v; }
 static int p2p_channels(hipStream_t out[3]) {
   int dev = g_device;
   if (dev < 0 && hipGetDevice(&dev) != hipSuccess) return MX_ERR_HIP;

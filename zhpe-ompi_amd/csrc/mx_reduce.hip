@@ -27,6 +27,7 @@
 #include "mx_dispatch.hpp"
 #include "mx_internal.h"
 #include "mx_mem.hpp"
+#include "mx_env.hpp"
 
 namespace mx {
 
@@ -312,23 +313,11 @@ static inline bool nt_small_wg(size_t work) { return work < ((size_t)1 << 31) * 
 
 // MX_REDUCE_W32=0 keeps 32-byte elements on the field-by-field element
 // kernel (A/B switch; results are identical)
-static bool conv_w32() {
-  static const int on = [] {
-    const char *e = getenv("MX_REDUCE_W32");
-    return (e && *e == '0') ? 0 : 1;
-  }();
-  return on != 0;
-}
+static bool conv_w32() { static const bool v = env_default_on("MX_REDUCE_W32"); return v; }
 
 // MX_REDUCE_W32T=0: 32-byte elements move per element (two accesses 32
 // bytes apart) instead of through LDS (A/B switch; results are identical)
-static bool w32_lds() {
-  static const int on = [] {
-    const char *e = getenv("MX_REDUCE_W32T");
-    return (e && *e == '0') ? 0 : 1;
-  }();
-  return on != 0;
-}
+static bool w32_lds() { static const bool v = env_default_on("MX_REDUCE_W32T"); return v; }
 
 // launches that carry their own completion mark: grids of at most
 // kMarkFlags workgroups.  A 256-lane launch for count elements has at most
@@ -348,13 +337,7 @@ constexpr size_t kFusedMarkMax = (size_t)kMarkFlags * 256 - 16;
 // tested from another process: tests/test_op_consumer_gpu.py (8 processes,
 // coll/base recursive doubling through op/mi355x, each step's result copied
 // by the peer through an IPC mapping as soon as the handler returns).
-static bool fused_mark() {
-  static const int on = [] {
-    const char *e = getenv("MX_FUSED_MARK");
-    return (e && *e == '0') ? 0 : 1;
-  }();
-  return on != 0;
-}
+static bool fused_mark() { static const bool v = env_default_on("MX_FUSED_MARK"); return v; }
 
 // The mark rides on a launch only if its grid has a flag per workgroup
 // (kMarkFlags); a larger grid -- e.g. a 64-lane non-temporal instance forced

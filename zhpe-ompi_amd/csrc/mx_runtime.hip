@@ -11,6 +11,7 @@
 #include <vector>
 #include "mx_internal.h"
 #include "mx_mem.hpp"
+#include "mx_env.hpp"
 
 namespace mx {
 int g_num_cus = 256;
@@ -94,13 +95,7 @@ pthread_mutex_t g_ptr_mu = PTHREAD_MUTEX_INITIALIZER;
 
 // MX_PTR_CACHE=0 disables the cache (the before/after measurement of
 // profiles/r02/op_call_cost.txt)
-static bool ptr_cache_on() {
-  static const bool on = [] {
-    const char *e = getenv("MX_PTR_CACHE");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
+static bool ptr_cache_on() { static const bool v = env_default_on("MX_PTR_CACHE"); return v; }
 
 extern "C" int mx_is_device_ptr(const void *p) {
   if (!p) return 0;
