@@ -65,7 +65,8 @@ int mx_ddt_span(const mx_ddt_t *ddt, size_t count, int64_t *lo, int64_t *hi);
 int mx_ddt_set_path(mx_ddt_t *ddt, int path);
 /* The kernel family of the last mx_pack / mx_unpack on this datatype:
  * 1 copy (contiguous), 2 vector, 3 granule, 4 byte map, 5 piece,
- * 6 block, 7 tile / pipelined tile; 0 before the first call. */
+ * 6 block, 7 tile / pipelined tile; 0 before the first call (enum Path in
+ * csrc/mx_convertor.hip names them; Datatype.PATHS in mxompi). */
 int mx_ddt_last_path(const mx_ddt_t *ddt);
 
 /* Pack bytes [offset, offset+len) of the packed stream of `count`

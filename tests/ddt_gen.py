@@ -6,7 +6,7 @@ Three things live here, none of which looks into the library:
 * a record emitter: a description tree of `Elem` and `Loop` nodes becomes the
   committed-description bytes mx_ddt_create reads (ELEM / LOOP / END_LOOP
   records of 32 bytes, the layouts of RecElem / RecLoop in
-  csrc/mx_convertor.hip and of rec_elem / rec_loop in oracle/mx_oracle_ddt.c),
+  csrc/mx_ddt_layout.hip and of rec_elem / rec_loop in oracle/mx_oracle_ddt.c),
   nested loops included, closed by the final END_LOOP;
 * an independent index map: a numpy walk of the same tree gives, for every
   packed byte of one instance, its user offset, so that

@@ -16,6 +16,13 @@
 // displacements, strides and block sizes) into registers, and writes one
 // coalesced 16-byte store (unpack: one 16-byte load, scattered stores).
 // Algorithmic bytes per launch: 2 * packed bytes.
+//
+// This file holds the kernels and, after them, the host side: mx_ddt (a
+// layout and its uploaded tables), the environment switches (ConvEnv), and
+// mx_pack / mx_unpack as one launcher per kernel family that
+// convert<PACK>() asks in order.  The layout planning itself -- flattening,
+// the byte map, the piece and block tables, every tile size the kernels
+// trust -- is host-only code in mx_ddt_layout.hpp / mx_ddt_layout.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -31,32 +38,15 @@
 #include "mx_mem.hpp"
 #include "../../include/mx_convertor.h"
 #include "mx_env.hpp"
+#include "mx_ddt_layout.hpp"
 
 namespace mx {
 
-// Division by a run-time constant without a 64-bit divide: for numerators
-// n < 2^48, floor(n / d) = floor(n * m / 2^k) with k = 48 + ceil(log2 d),
-// m = ceil(2^k / d) (Granlund & Montgomery, PLDI'94, thm 4.2).
-struct Magic { uint64_t m; uint32_t k; uint32_t pad; };
-constexpr int kMagicBits = 48;
-
+// floor(n / d) for n < 2^kMagicBits through d's Magic (mx_ddt_layout.hpp)
 __host__ __device__ __forceinline__ uint64_t udiv(uint64_t n, const Magic &M) {
   return (uint64_t)(((unsigned __int128)n * M.m) >> M.k);
 }
 
-struct DRun {
-  int64_t disp;
-  uint64_t blen;     // bytes per block
-  uint64_t cnt1;     // inner block count
-  int64_t stride1;
-  uint64_t cnt2;     // outer repetition count
-  int64_t stride2;
-  uint64_t poff;     // packed offset of the run within one instance
-  uint64_t bytes;    // blen * cnt1 * cnt2
-  Magic mblen, mcnt1;
-};
-
-constexpr int kCB = 256;
 constexpr int kLdsRuns = 512;    // run tables up to 48 KiB are staged in LDS
 
 struct Pos {
@@ -675,19 +665,7 @@ __global__ void __launch_bounds__(kCB) k_pack_tile_pipe(ConvArgs a, int nruns_ld
 //     wave writes 64 consecutive pieces at once and every user line is
 //     complete within a few instructions.  Gap bytes are never written.
 // ---------------------------------------------------------------------------
-constexpr uint32_t kBmapMaxS = 65535;      // packed bytes per instance (piece soff is 16-bit)
-constexpr size_t kBmapLds = 20480;         // PACK: map bytes staged in LDS
-constexpr int kBmapSpan = 24576;           // PACK: user span staged per tile
-constexpr int kBmapSpans[3] = {12288, kBmapSpan, 49152};   // MX_CONV_BMAP_SPAN choices
-constexpr int kPieceStage = 16384;         // UNPACK: packed bytes staged per tile
-
-struct DPiece {
-  int32_t uoff;       // user offset from the instance origin
-  uint16_t soff;      // stream offset within the instance
-  uint8_t lg;         // width = 1 << lg bytes (user address aligned to it)
-  uint8_t pad;
-};
-
+// (kBmapMaxS, kBmapLds, kBmapSpan[s], kPieceStage and DPiece: mx_ddt_layout.hpp)
 struct BmapArgs {
   const void *map;         // M[S]: user offset of packed byte b minus umin
   uint32_t S;
@@ -1330,13 +1308,7 @@ __global__ void __launch_bounds__(kCB) k_pack_piece(PieceArgs a) {
 // Only lines holding data are touched on the user side and no lane walks
 // more than its own 16 bytes.
 // ---------------------------------------------------------------------------
-constexpr uint32_t kBlkCap = 1024;         // staged blocks per tile (16 KiB of LDS)
-constexpr uint32_t kBlkG = 256;            // tfirst granularity (instance stream bytes)
-
-// device block table entry (8 B): user offset from the instance origin and
-// stream offset; a block's length is the next entry's soff minus its own
-// (the table carries one sentinel entry with soff = the instance size)
-struct DBlk { int32_t uoff; uint32_t soff; };
+// (kBlkCap, kBlkG and the device block table entry DBlk: mx_ddt_layout.hpp)
 struct DBlkL { int32_t uoff; uint32_t soff, send; };   // an entry with its end, in registers
 struct SBlk { int64_t u; int32_t s; uint32_t len; };   // u: from instance ia's origin; s: from the tile start
 
@@ -1526,7 +1498,6 @@ __device__ __forceinline__ void blk_map(const BlkArgs &a, uint32_t n, uint64_t u
   }
 }
 
-constexpr uint32_t kBlkMaxT = 65536;       // largest tile (packed-memory bytes)
 constexpr uint32_t kBlkMaxMap = kBlkMaxT / 64;
 
 // Lane l owns the 16-byte packed-memory granules l, l + kCB, ... of the
@@ -1717,7 +1688,6 @@ __global__ void __launch_bounds__(kCB) k_convert_blk(BlkArgs a) {
 // alignbyte when the granule lies inside one block, part by part otherwise
 // -- and leaves with one 16-byte store.  User lines are read once, whole;
 // no lane waits on a dependent global load after the staging.
-constexpr uint32_t kBlkSpan = 24576;
 constexpr int kBlkSpanPer = kBlkSpan / 16 / kCB;   // uint4 per lane
 
 // (pointer arithmetic, not an integer round trip: the compiler must keep
@@ -1853,29 +1823,23 @@ __global__ void __launch_bounds__(kCB) k_pack_blk_span(BlkArgs a, uint32_t cap) 
 
 using namespace mx;
 
-struct HBlk { int64_t uoff; uint32_t soff; uint32_t len; };   // host side of the block table (blk_tab)
+// The kernel family of a call, as mx_ddt_last_path reports it
+// (include/mx_convertor.h; Datatype.PATHS in mxompi/__init__.py).
+enum Path {
+  PATH_NONE = 0,      // before the first call
+  PATH_COPY = 1,      // contiguous: one copy
+  PATH_VEC = 2,       // k_pack_vec_span / k_convert_vec
+  PATH_GRANULE = 3,   // k_convert
+  PATH_BMAP = 4,      // k_pack_bmap
+  PATH_PIECE = 5,     // k_pack_piece / k_unpack_piece / k_unpack_piece_direct
+  PATH_BLOCK = 6,     // k_convert_blk / k_pack_blk_span
+  PATH_TILE = 7       // k_convert_tile / k_pack_tile_pipe
+};
 
 struct mx_ddt {
-  std::vector<DRun> host;
-  DRun *dev;
-  size_t size;
-  int64_t lb, ub;
-  uint64_t gcd_all;  // gcd of every disp/stride/blen/extent (access unit)
-  Magic mS;          // divide by size
-  bool monotonic;    // user addresses strictly increase along the stream
-  // byte map of one instance (size <= kBmapMaxS): bmap[b] = user offset of
-  // packed byte b.  PACK kernel k_pack_bmap stages (bmap - umin) as 16-bit
-  // (user span < 64 KiB) or 32-bit words when they fit kBmapLds.
-  std::vector<int32_t> bmap;
-  void *map_dev = nullptr;
-  int map16 = 0;
-  int64_t umin = 0, uspan = 0;
-  uint64_t bmap_T = 0;             // stream bytes per PACK tile (0: no PACK kernel)
-  uint64_t bmap_Ts[3] = {0, 0, 0}; // the same for staged spans kBmapSpans[0..2] (bmap_T = [1])
-  bool bmap_quad = false;          // the PACK kernel stages the map as quads (BmapArgs::qsh)
-  bool bmap_cw = false;            // >= 90 % of packed dwords are 4 user-contiguous bytes (BmapArgs::cw)
-  bool bmap_word = false;          // every dword at a phase 4k is (BmapArgs::word)
-  bool piece_pack = false;         // PACK takes the piece kernel (wide word-aligned pieces, build_bmap)
+  DdtLayout lay;                   // runs, sizes, byte map and its tiles (mx_ddt_layout.hpp)
+  DRun *dev = nullptr;             // lay.runs
+  void *map_dev = nullptr;         // lay.bmap - lay.umin, 16- or 32-bit (lay.map16)
   // piece tables per user-origin alignment (address mod 16), built on first
   // use: UNPACK kernel k_unpack_piece
   struct PieceTab {
@@ -1909,460 +1873,232 @@ struct mx_ddt {
     int built = 0;                 // 1 ok, -1 not applicable
   } btab;
   int force_blk = 0;               // mx_ddt_set_path(MX_DDT_PATH_BLOCK)
-  std::atomic<int> last_path{0};   // mx_ddt_last_path
+  std::atomic<int> last_path{PATH_NONE};   // mx_ddt_last_path
   std::mutex mu;
 };
 
 namespace {
 
-// dt_elem_desc record views (opal_datatype_internal.h:146-196)
-struct RecElem { uint16_t flags, type; uint32_t count; uint64_t blocklen; int64_t extent; int64_t disp; };
-struct RecLoop { uint16_t flags, type; uint32_t items; uint32_t loops; uint32_t pad; uint64_t unused; int64_t extent; };
-static_assert(sizeof(RecElem) == 32 && sizeof(RecLoop) == 32, "dt_elem_desc is 32 bytes");
+// The convertor's environment switches, read once per process (conv_env):
+// at the first datatype creation at the latest, so before any launch.
+struct ConvEnv {
+  // MX_CONV_BMAP_INST=0: the byte-map PACK's tiles of non-monotonic layouts
+  // stay multiples of 256 stream bytes instead of whole instances (A/B switch;
+  // used at datatype creation)
+  bool bmap_inst = env_default_on("MX_CONV_BMAP_INST");
 
-constexpr uint16_t T_LOOP = 0, T_END_LOOP = 1, T_LB = 2, T_UB = 3;
-constexpr uint16_t F_DATA = 0x0100;
-constexpr size_t kMaxRuns = (size_t)1 << 22;
+  // BLOCK kernel geometry (A/B switches; results are identical):
+  // MX_CONV_BLK_T = largest tile (4096 .. 65536 packed bytes, default 16384),
+  // MX_CONV_BLK_NG = granules per lane in flight (1, 2, 4; default, here 0: 2
+  // for PACK -- layouts the span kernel does not take -- and 4 for UNPACK:
+  // measured, profiles/r03/convertor_r3.txt),
+  // MX_CONV_BLK_W4=0 stores every UNPACK granule in naturally aligned pieces.
+  uint64_t blk_tmax = [] {
+    const char *e = getenv("MX_CONV_BLK_T");
+    const long v = e ? atol(e) : 16384;
+    return (uint64_t)((v >= 4096 && v <= (long)kBlkMaxT && (v & (v - 1)) == 0) ? v : 16384);
+  }();
+  int blk_ng = [] {
+    const char *e = getenv("MX_CONV_BLK_NG");
+    const int v = e ? atoi(e) : 0;
+    return (v == 1 || v == 2 || v == 4) ? v : 0;
+  }();
+  int blk_w4 = env_default_on("MX_CONV_BLK_W4");
+  // MX_CONV_BLK_SPAN=0 keeps PACK of monotonic layouts on the granule
+  // kernel instead of the span-staged one (A/B switch; used when the block
+  // table is planned).
+  bool blk_span = env_default_on("MX_CONV_BLK_SPAN");
 
-static const uint64_t kBasicLP64[MX_OPAL_NBASIC] = {
-    0, 0, 0, 0,            // LOOP END_LOOP LB UB
-    1, 2, 4, 8, 16,        // INT1 INT2 INT4 INT8 INT16
-    1, 2, 4, 8, 16,        // UINT1 .. UINT16
-    2, 4, 8, 16, 16,       // FLOAT2 FLOAT4 FLOAT8 FLOAT12 (long double: 16 B) FLOAT16
-    4, 8, 16, 32,          // SHORT_FLOAT_COMPLEX FLOAT_COMPLEX DOUBLE_COMPLEX LONG_DOUBLE_COMPLEX
-    1, 4, 0                // BOOL WCHAR UNAVAILABLE
+  // MX_CONV_VEC=0 sends single-run layouts to the general kernels instead
+  // (A/B measurement switch; results are identical).
+  bool vec = env_default_on("MX_CONV_VEC");
+
+  // MX_CONV_PIPE=0 sends PACK to the one-tile-per-workgroup kernel instead
+  // of the pipelined one (A/B switch; results are identical).
+  bool pipe = env_default_on("MX_CONV_PIPE");
+
+  // MX_CONV_BMAP=0 keeps small irregular instances on the run-walking tile
+  // kernels (A/B switch; results are identical).
+  bool bmap = env_default_on("MX_CONV_BMAP");
+
+  // MX_CONV_BMAP_PACK=0 sends PACK of small dense instances to the piece
+  // kernel instead of the byte-map kernel (A/B switch).
+  bool bmap_pack = env_default_on("MX_CONV_BMAP_PACK");
+
+  // MX_CONV_PPACK=0 keeps PACK of layouts the byte map does not take on the
+  // run-walking kernels instead of the piece kernel (A/B switch).
+  bool ppack = env_default_on("MX_CONV_PPACK");
+
+  // MX_CONV_BMAP_DW=0 gives each lane of the byte-map PACK kernel 16 packed
+  // bytes (one 16-byte store) instead of one dword per step (A/B switch).
+  bool bmap_dw = env_default_on("MX_CONV_BMAP_DW");
+
+  // MX_CONV_BLK: 0 keeps every layout off the BLOCK kernels, 1 (default)
+  // sends instances without a byte map (> kBmapMaxS packed bytes) to them,
+  // 2 also small instances (A/B against the byte-map / piece kernels; results
+  // are identical).
+  int blk_mode = [] {
+    const char *e = getenv("MX_CONV_BLK");
+    const int v = e ? atoi(e) : 1;
+    return (v >= 0 && v <= 2) ? v : 1;
+  }();
+
+  // MX_CONV_BMAP_PIPE=0 runs the byte-map PACK kernel without the span
+  // prefetch of the next tile (A/B switch; results are identical).
+  bool bmap_pipe = env_default_on("MX_CONV_BMAP_PIPE");
+
+  // MX_CONV_BMAP_ALIGN=16|128: the byte-map PACK stages a tile's user span
+  // from its first 16-byte granule or from the start of that granule's
+  // 128-byte line, so that a wave's 1 KiB loads cover whole lines
+  uint64_t bmap_align = [] {
+    const char *e = getenv("MX_CONV_BMAP_ALIGN");
+    return (uint64_t)((e && atoi(e) == 16) ? 16 : 128);
+  }();
+
+  // MX_CONV_BMAP_QUAD=0 stages the byte-map PACK's map as one row also where
+  // S % 4 != 0 (A/B switch; results identical)
+  bool bmap_quad = env_default_on("MX_CONV_BMAP_QUAD");
+
+  // MX_CONV_BMAP_CW=0: the byte-map PACK reads every packed byte on its own
+  // also where whole waves of packed dwords are user-contiguous (A/B switch)
+  bool bmap_cw = env_default_on("MX_CONV_BMAP_CW");
+
+  // MX_CONV_BMAP_NT=0: the byte-map PACK reads the user span and writes the
+  // packed stream with ordinary accesses instead of non-temporal ones (A/B
+  // switch).  The span is staged with one coalesced 16-byte load per lane, the
+  // pattern whose floor is 1.23x faster non-temporal at 256 MiB
+  // (tools/pack_floor_probe split-nt vs split-plain, profiles/r05/pack_floor_r5j.txt)
+  bool bmap_nt = env_default_on("MX_CONV_BMAP_NT");
+
+  // MX_CONV_VEC_NT=0: the VEC and VEC-span PACK kernels keep ordinary accesses
+  // at the streaming sizes too (A/B switch)
+  bool vec_nt = env_default_on("MX_CONV_VEC_NT");
+
+  // MX_CONV_UNPACK_NTLD=1: the UNPACK kernels read the packed stream with
+  // non-temporal loads at the streaming sizes (A/B switch, off: -5 % / +5 %
+  // on indexed at 256 MiB / 1 GiB, within 1 % elsewhere, profiles/r05/conv_ab_r5y.txt;
+  // the unpack is bound by its partial-line stores)
+  bool unpack_ntld = env_default_off("MX_CONV_UNPACK_NTLD");
+
+  // MX_CONV_UNPACK_U32=0: the piece UNPACK kernel's store loop in 64-bit
+  // stream coordinates (round 4's form; A/B switch)
+  bool unpack_u32 = env_default_on("MX_CONV_UNPACK_U32");
+
+  // MX_CONV_BMAP_WORD=1: the byte-map PACK stages a word map for word-piece
+  // layouts (A/B switch, off: indexed 112 -> 137 us at 256 MiB with it, BLACS
+  // equal, profiles/r05/conv_r5r.txt -- the gather gets shorter and the tile's
+  // span prefetch, which it hid, is waited for instead)
+  bool bmap_word = env_default_off("MX_CONV_BMAP_WORD");
+
+  // MX_CONV_BMAP_UNROLL=0: one packed dword per lane per step in the byte-map
+  // PACK's gather instead of kBmapU (A/B switch)
+  bool bmap_unroll = env_default_on("MX_CONV_BMAP_UNROLL");
+
+  // MX_CONV_BMAP_SPAN=12288|24576|49152: user span the byte-map PACK stages
+  // per tile (A/B switch; the tile's stream bytes follow from it; unset, here
+  // -1: 24 KiB where five workgroups fit a CU, else 12 KiB)
+  int bmap_span_idx = [] {
+    const char *e = getenv("MX_CONV_BMAP_SPAN");
+    if (!e) return -1;                                   // by the map's size
+    const long x = atol(e);
+    return x == kBmapSpans[0] ? 0 : x == kBmapSpans[2] ? 2 : 1;
+  }();
+
+  // MX_CONV_UNPACK_PIPE=1 runs the piece UNPACK kernel with the register
+  // prefetch of the next tile's packed range (A/B switch, off: measured
+  // slower; results are identical).
+  bool unpack_pipe = env_default_off("MX_CONV_UNPACK_PIPE");
+
+  // The piece UNPACK form: MX_CONV_UNPACK_DIRECT=0 always the LDS-staged tile
+  // kernel (here 1), =1 always one piece per lane (2), unset (0): measured
+  // per datatype (mx_ddt::up_choice).  Results are identical.
+  int unpack_direct = [] {
+    const char *e = getenv("MX_CONV_UNPACK_DIRECT");
+    return (e && *e == '0') ? 1 : (e && *e == '1') ? 2 : 0;
+  }();
+
+  // MX_CONV_VEC_SPAN=0 packs periodic small-block vectors through the VEC
+  // kernel instead of k_pack_vec_span (A/B switch; results are identical).
+  bool vec_span = env_default_on("MX_CONV_VEC_SPAN");
+
+  // MX_CONV_PIPE_GEOM selects the pipelined tile PACK's geometry (A/B
+  // measurement; results are identical): 0 = 8192 x 24 KiB span, 1 = 9216 x
+  // 16 KiB, 2 = 9216 x 28 KiB, 3 = 8192 x 16 KiB.  0 is fastest on every type
+  // measured (profiles/r02/convertor_r2.txt): the bank-conflict-free
+  // 36-byte stretches of 1 / 2 lose more to the tile / occupancy change
+  // than the conflicts cost (20k of ~4M cycles per wave).
+  int pipe_geom = [] {
+    const char *e = getenv("MX_CONV_PIPE_GEOM");
+    const int v = e ? atoi(e) : 0;
+    return (v >= 0 && v <= 3) ? v : 0;
+  }();
+
+  // Tile size of the TILE kernels (MX_CONV_TP = 2048 / 4096 / 8192 for
+  // measurement; results are identical).
+  int tile_bytes = [] {
+    const char *e = getenv("MX_CONV_TP");
+    const int v = e ? atoi(e) : 0;
+    return (v == 2048 || v == 4096 || v == 8192) ? v : 8192;
+  }();
 };
 
-static bool contiguous_single(const DRun &r) { return r.cnt1 == 1 && r.cnt2 == 1; }
-
-static void push_run(std::vector<DRun> &out, DRun r) {
-  if (r.bytes == 0) return;
-  // a 1-level run whose blocks touch is one contiguous block
-  if (r.cnt2 == 1 && r.cnt1 > 1 && r.stride1 == (int64_t)r.blen) { r.blen *= r.cnt1; r.cnt1 = 1; r.stride1 = 0; }
-  if (!out.empty()) {
-    DRun &p = out.back();
-    if (contiguous_single(p) && contiguous_single(r) && p.disp + (int64_t)p.blen == r.disp) {
-      p.blen += r.blen;
-      p.bytes += r.bytes;
-      return;
-    }
-  }
-  out.push_back(r);
+const ConvEnv &conv_env() {
+  static const ConvEnv e;
+  return e;
 }
 
-static int flatten(const uint8_t *recs, size_t lo, size_t hi, int64_t base, const uint64_t *bs,
-                   std::vector<DRun> &out) {
-  size_t i = lo;
-  while (i < hi) {
-    RecElem e;
-    memcpy(&e, recs + 32 * i, 32);
-    if (e.type == T_END_LOOP) return MX_SUCCESS;   // terminator of this level
-    if (e.type == T_LOOP) {
-      RecLoop L;
-      memcpy(&L, recs + 32 * i, 32);
-      if (L.items == 0 || i + L.items >= hi + 1) return MX_ERR_ARG;
-      std::vector<DRun> body;
-      int rc = flatten(recs, i + 1, i + L.items, 0, bs, body);
-      if (rc) return rc;
-      if (body.size() == 1 && body[0].cnt2 == 1) {
-        DRun r = body[0];
-        r.disp += base;
-        if (contiguous_single(r)) {          // loop of one contiguous block
-          r.cnt1 = L.loops;
-          r.stride1 = L.extent;
-        } else {
-          r.cnt2 = L.loops;
-          r.stride2 = L.extent;
-        }
-        r.bytes = r.blen * r.cnt1 * r.cnt2;
-        push_run(out, r);
-      } else {
-        if (out.size() + body.size() * (size_t)L.loops > kMaxRuns) return MX_ERR_UNSUPPORTED;
-        for (uint32_t l = 0; l < L.loops; l++)
-          for (DRun r : body) {
-            r.disp += base + (int64_t)l * L.extent;
-            push_run(out, r);
-          }
-      }
-      i += L.items + 1;
-      continue;
-    }
-    if (e.type == T_LB || e.type == T_UB || !(e.flags & F_DATA)) { i++; continue; }
-    if (e.type >= MX_OPAL_NBASIC || bs[e.type] == 0) return MX_ERR_ARG;
-    DRun r;
-    r.disp = base + e.disp;
-    r.blen = e.blocklen * bs[e.type];
-    r.cnt1 = e.count;
-    r.stride1 = e.extent;
-    r.cnt2 = 1;
-    r.stride2 = 0;
-    r.bytes = r.blen * r.cnt1;
-    push_run(out, r);
-    if (out.size() > kMaxRuns) return MX_ERR_UNSUPPORTED;
-    i++;
-  }
-  return MX_SUCCESS;
-}
-
-static Magic make_magic(uint64_t d) {
-  Magic M;
-  int l = 0;
-  while (l < 64 && (((unsigned __int128)1) << l) < d) l++;
-  M.k = (uint32_t)(kMagicBits + l);
-  const unsigned __int128 two_k = ((unsigned __int128)1) << M.k;
-  M.m = (uint64_t)((two_k + d - 1) / d);
-  M.pad = 0;
-  return M;
-}
-
-// Every byte of the stream lies at a higher user address than the one
-// before it (runs, blocks and instances in address order, no overlap):
-// then a tile's bytes all lie in [addr(first), addr(last)].
-static bool is_monotonic(const std::vector<DRun> &runs, int64_t ext) {
-  if (runs.empty()) return false;
-  int64_t prev_end = INT64_MIN;   // one past the last byte so far
-  for (const DRun &r : runs) {
-    if (r.cnt1 > 1 && r.stride1 < (int64_t)r.blen) return false;
-    const int64_t inner = (int64_t)(r.cnt1 - 1) * r.stride1 + (int64_t)r.blen;
-    if (r.cnt2 > 1 && r.stride2 < inner) return false;
-    if (r.disp < prev_end) return false;
-    prev_end = r.disp + (int64_t)(r.cnt2 - 1) * r.stride2 + inner;
-  }
-  return prev_end <= ext + runs[0].disp;   // next instance starts after
-}
-
-static uint64_t gcd64(uint64_t a, uint64_t b) {
-  while (b) { uint64_t t = a % b; a = b; b = t; }
-  return a;
-}
-static uint64_t absg(int64_t v) { return v < 0 ? (uint64_t)(-v) : (uint64_t)v; }
-
-// Pieces of one instance for a user origin at address `al` mod 16: maximal
-// contiguous user runs in stream order, cut into naturally aligned
-// 1/2/4/8/16-byte pieces (aligned for every instance: the width also
-// divides the extent).
-static void cut_pieces(const mx_ddt *d, int al, std::vector<DPiece> &v) {
-  const uint64_t A = gcd64(16, absg(d->ub - d->lb));
-  const size_t S = d->bmap.size();
-  for (size_t b = 0; b < S;) {
-    size_t L = 1;
-    while (b + L < S && d->bmap[b + L] == d->bmap[b] + (int32_t)L) L++;
-    for (size_t pos = 0; pos < L;) {
-      const int64_t x = (int64_t)d->bmap[b] + (int64_t)pos;
-      const uint64_t addr = (uint64_t)(((al + x) % 16 + 16) % 16);
-      uint64_t w = 16;
-      while (w > 1 && (addr % w || w > L - pos || A % w)) w >>= 1;
-      DPiece pc;
-      pc.uoff = (int32_t)x;
-      pc.soff = (uint16_t)(b + pos);
-      pc.lg = (uint8_t)__builtin_ctzll(w);
-      pc.pad = 0;
-      v.push_back(pc);
-      pos += w;
-    }
-    b += L;
-  }
-}
-
-// Byte map of one instance: bmap[b] = user offset of packed byte b.  Also
-// fixes the PACK tile: the largest multiple of 256 stream bytes (<= 16 KiB)
-// whose user span, rounded out to 16 bytes, always fits kBmapSpan -- whole
-// instances for a non-monotonic layout, [addr(first), addr(last)] for a
-// monotonic one.
-// MX_CONV_BMAP_INST=0: the byte-map PACK's tiles of non-monotonic layouts
-// stay multiples of 256 stream bytes instead of whole instances (A/B switch;
-// read at datatype creation)
-static bool conv_bmap_inst_tiles() { static const bool v = env_default_on("MX_CONV_BMAP_INST"); return v; }
-
-static void build_bmap(mx_ddt *d) {
-  const int64_t ext = d->ub - d->lb;
-  const uint64_t S = d->size;
-  if (S == 0 || S > kBmapMaxS || ext <= 0) return;
-  std::vector<int32_t> m;
-  m.reserve(S);
-  int64_t lo = INT64_MAX, hi = INT64_MIN;
-  for (const DRun &r : d->host)
-    for (uint64_t l2 = 0; l2 < r.cnt2; l2++)
-      for (uint64_t l1 = 0; l1 < r.cnt1; l1++)
-        for (uint64_t o = 0; o < r.blen; o++) {
-          const int64_t u = r.disp + (int64_t)l2 * r.stride2 + (int64_t)l1 * r.stride1 + (int64_t)o;
-          if (u < INT32_MIN || u > INT32_MAX) return;
-          m.push_back((int32_t)u);
-          lo = std::min(lo, u);
-          hi = std::max(hi, u + 1);
-        }
-  if (m.size() != S) return;
-  d->bmap.swap(m);
-  d->umin = lo;
-  d->uspan = hi - lo;
-  // 16-bit map entries when every entry of the kernel's wrapped table
-  // (bmap + ext for the three bytes past an instance) fits
-  d->map16 = d->uspan + (int64_t)((S + 2) / S) * ext <= 65536;
-  // PACK kernel choice: pieces of >= 8 bytes on average that all land on
-  // whole packed words move with few wide accesses through the piece kernel;
-  // narrow or misaligned pieces go through the byte map, whose cost per
-  // byte is flat.  Measured at 1 GiB (profiles/r02/convertor_r2.txt): lower
-  // triangle (8-byte pieces) piece 3.58 vs byte map 2.28 TB/s; indexed /
-  // BLACS (4-byte) 2.66 / 2.85 vs 3.40 / 3.05; struct (misaligned) 2.46 vs
-  // 3.41; 8-byte struct types equal within 2 %.
-  {
-    std::vector<DPiece> v;
-    cut_pieces(d, 0, v);
-    bool words = true;
-    for (const DPiece &p : v) words = words && p.lg >= 2 && (p.soff & 3) == 0;
-    d->piece_pack = words && !v.empty() && S >= 8 * v.size();
-  }
-  // The byte map is staged only for dense layouts (<= 4 user bytes per
-  // packed byte; a sparse one reads mostly gaps -- ref_matrix_borders at 23:
-  // 0.83 -> 0.42 TB/s) and maps small enough for >= 3 workgroups per CU
-  // (ref_upper_matrix_60's 29 KiB map: 1.32 -> 1.25 TB/s)
-  if ((S + 3) * (d->map16 ? 2 : 4) > kBmapLds || ext > 4 * (int64_t)S || d->uspan > 4 * (int64_t)S) return;
-  d->bmap_quad = S % 4 != 0 && 4 * S * (d->map16 ? 2 : 4) <= kBmapLds;
-  {                                // packed dwords whose 4 bytes are user-contiguous, by instance phase
-    auto Ux = [&](uint64_t x) { return (int64_t)(x / S) * ext + d->bmap[x % S]; };
-    uint64_t c = 0;
-    for (uint64_t b = 0; b < S; b++) c += Ux(b + 3) == Ux(b) + 3 && Ux(b + 1) == Ux(b) + 1 && Ux(b + 2) == Ux(b) + 2;
-    d->bmap_cw = c * 10 >= 9 * S;
-    uint64_t cwd = 0;                // at the phases a dword of a 16-aligned tile starts at
-    for (uint64_t b = 0; b < S; b += 4)
-      cwd += Ux(b + 3) == Ux(b) + 3 && Ux(b + 1) == Ux(b) + 1 && Ux(b + 2) == Ux(b) + 2;
-    d->bmap_word = S % 4 == 0 && cwd == S / 4;
-  }
-  // user bytes a tile of T stream bytes starting at instance byte b touches
-  auto U = [&](uint64_t x) { return (int64_t)(x / S) * ext + d->bmap[x % S]; };
-  auto worst = [&](uint64_t T) {
-    if (!d->monotonic) return (int64_t)(((T - 1) / S + 1) * (uint64_t)ext) + d->uspan;
-    int64_t w = 0;
-    for (uint64_t b = 0; b < S; b++) w = std::max<int64_t>(w, U(b + T - 1) - U(b) + 1);
-    return w;
-  };
-  // the largest T (a multiple of 256, at most 2/3 of the span) whose worst
-  // user span + 160 fits: the span staged from a 128-byte line start
-  // (MX_CONV_BMAP_ALIGN) plus its 16-byte rounding up.  worst() grows with T.
-  for (int k = 0; k < 3; k++) {
-    const int64_t span = kBmapSpans[k];
-    uint64_t lo = 0, hi = (uint64_t)span * 2 / 3 / 256;      // in units of 256
-    while (lo < hi) {
-      const uint64_t mid = (lo + hi + 1) / 2;
-      if (worst(mid * 256) + 160 <= span) lo = mid;
-      else hi = mid - 1;
-    }
-    d->bmap_Ts[k] = lo * 256;
-    // a layout that is not monotonic stages whole instances per tile; when
-    // S % 16 == 0 a tile of exactly k instances starts (from offset 0) on an
-    // instance boundary and stages k of them, not the k + 1 a tile cut
-    // mid-instance does (indexed: 12.9 instead of 19.3 KiB per 10 KiB of stream)
-    if (!d->monotonic && S % 16 == 0) {
-      const int64_t kk = (span - 160 - d->uspan) / ext;   // worst(kk * S) + 160 <= span
-      if (kk >= 1 && (uint64_t)kk * S >= 256 && (uint64_t)kk * S <= (uint64_t)span * 2 / 3 &&
-          worst((uint64_t)kk * S) + 160 <= span && conv_bmap_inst_tiles())
-        d->bmap_Ts[k] = (uint64_t)kk * S;
-    }
-  }
-  d->bmap_T = d->bmap_Ts[1];
-}
-
-// The piece table for a user origin at address `al` mod 16 (cut_pieces),
+// The piece table for a user origin at address `al` mod 16 (plan_pieces),
 // uploaded, with its tile size.  Caller holds d->mu.
-static mx_ddt::PieceTab *piece_tab(mx_ddt *d, int al) {
+mx_ddt::PieceTab *piece_tab(mx_ddt *d, int al) {
   mx_ddt::PieceTab &P = d->ptab[al];
   if (P.built) return P.built > 0 ? &P : nullptr;
   P.built = -1;
-  const size_t S = d->bmap.size();
   std::vector<DPiece> v;
-  cut_pieces(d, al, v);
-  const uint32_t npi = (uint32_t)v.size();
-  // pieces per tile: ~8 KiB of stream, staged bytes (+ alignment slop) <= kPieceStage
-  auto window = [&](uint32_t K) {
-    uint64_t mx = 0;
-    for (uint32_t j = 0; j < npi; j++) {
-      const uint64_t e = (uint64_t)j + K - 1;
-      const DPiece &pe = v[e % npi];
-      const uint64_t end = (e / npi) * S + pe.soff + (1u << pe.lg);
-      mx = std::max<uint64_t>(mx, end - v[j].soff);
-    }
-    return mx;
-  };
-  uint64_t K = std::max<uint64_t>(kCB, std::min<uint64_t>(4096, (8192ull * npi / S) / kCB * kCB));
-  while (K > kCB && window((uint32_t)K) + 32 > (uint64_t)kPieceStage) K -= kCB;
-  if (window((uint32_t)K) + 32 > (uint64_t)kPieceStage) return nullptr;
-  if (hipMalloc((void **)&P.dev, npi * sizeof(DPiece)) != hipSuccess) { P.dev = nullptr; return nullptr; }
-  if (hipMemcpy(P.dev, v.data(), npi * sizeof(DPiece), hipMemcpyHostToDevice) != hipSuccess) {
+  uint32_t K = 0;
+  if (!plan_pieces(d->lay, al, v, K)) return nullptr;
+  const size_t bytes = v.size() * sizeof(DPiece);
+  if (hipMalloc((void **)&P.dev, bytes) != hipSuccess) { P.dev = nullptr; return nullptr; }
+  if (hipMemcpy(P.dev, v.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) {
     release_later(P.dev, REL_DEV);
     P.dev = nullptr;
     return nullptr;
   }
   P.host.swap(v);
-  P.K = (uint32_t)K;
+  P.K = K;
   P.built = 1;
   return &P;
 }
 
-// BLOCK kernel geometry (A/B switches; results are identical):
-// MX_CONV_BLK_T = largest tile (4096 .. 65536 packed bytes, default 16384),
-// MX_CONV_BLK_NG = granules per lane in flight (1, 2, 4; default 2 for
-// PACK -- layouts the span kernel does not take -- and 4 for UNPACK:
-// measured, profiles/r03/convertor_r3.txt),
-// MX_CONV_BLK_W4=0 stores every UNPACK granule in naturally aligned pieces.
-static uint64_t conv_blk_tmax() {
-  static const uint64_t t = [] {
-    const char *e = getenv("MX_CONV_BLK_T");
-    const long v = e ? atol(e) : 16384;
-    return (uint64_t)((v >= 4096 && v <= (long)kBlkMaxT && (v & (v - 1)) == 0) ? v : 16384);
-  }();
-  return t;
-}
-static int conv_blk_ng(bool pack) {
-  static const int g = [] {
-    const char *e = getenv("MX_CONV_BLK_NG");
-    const int v = e ? atoi(e) : 0;
-    return (v == 1 || v == 2 || v == 4) ? v : 0;
-  }();
-  return g ? g : (pack ? 2 : 4);
-}
-// MX_CONV_BLK_SPAN=0 keeps PACK of monotonic layouts on the granule
-// kernel instead of the span-staged one (A/B switch).
-static bool conv_blk_span() { static const bool v = env_default_on("MX_CONV_BLK_SPAN"); return v; }
-static int conv_blk_w4() { static const int v = env_default_on("MX_CONV_BLK_W4"); return v; }
-
-// The block table of k_convert_blk (caller holds d->mu): the instance's
-// contiguous user blocks in stream order (touching blocks merged), tfirst[k]
-// = the block holding instance stream byte k * kBlkG (one entry past the
-// last stretch, so [tfirst[k], tfirst[k + 1]] always brackets the search),
-// and the tile T: the largest of 16 KiB .. 512 B of packed memory whose
-// stream stretch never overlaps more than kBlkCap blocks (a T-byte stretch
-// overlaps at most the blocks from b to the one holding end(b) - 2 + T,
-// over every block b, across instance boundaries).
-static mx_ddt::BlkTab *blk_tab(mx_ddt *d) {
+// The block table of k_convert_blk (plan_blocks), uploaded.  Caller holds
+// d->mu.
+mx_ddt::BlkTab *blk_tab(mx_ddt *d) {
   mx_ddt::BlkTab &B = d->btab;
   if (B.built) return B.built > 0 ? &B : nullptr;
   B.built = -1;
-  const uint64_t S = d->size;
-  const int64_t ext = d->ub - d->lb;
-  constexpr uint64_t kMaxBlocks = (uint64_t)1 << 22;
-  if (S == 0 || S >= ((uint64_t)1 << 31) || ext <= 0) return nullptr;
-  std::vector<HBlk> v;
-  uint64_t soff = 0;
-  for (const DRun &r : d->host) {
-    if (v.size() + r.cnt1 * r.cnt2 > kMaxBlocks + 1) return nullptr;
-    for (uint64_t l2 = 0; l2 < r.cnt2; l2++)
-      for (uint64_t l1 = 0; l1 < r.cnt1; l1++) {
-        const int64_t u = r.disp + (int64_t)l2 * r.stride2 + (int64_t)l1 * r.stride1;
-        if (!v.empty() && v.back().uoff + (int64_t)v.back().len == u && v.back().len + r.blen < ((uint64_t)1 << 31)) {
-          v.back().len += (uint32_t)r.blen;
-        } else {
-          HBlk b;
-          b.uoff = u;
-          b.soff = (uint32_t)soff;
-          b.len = (uint32_t)r.blen;
-          v.push_back(b);
-        }
-        soff += r.blen;
-      }
-  }
-  if (v.empty() || v.size() > kMaxBlocks || soff != S) return nullptr;
-  const uint64_t nb = v.size();
-  auto max_overlap = [&](uint64_t T) {
-    uint64_t mx = 0, j = 0;
-    for (uint64_t b = 0; b < nb; b++) {
-      const uint64_t last = (uint64_t)v[b].soff + v[b].len - 1 + T - 1;   // end(b) - 2 + T
-      if (j < b) j = b;
-      // advance j to the block holding `last` (monotonic in b)
-      while (true) {
-        const uint64_t jn = j + 1, i = jn / nb;
-        const uint64_t start = i * S + v[jn - i * nb].soff;
-        if (start > last) break;
-        j = jn;
-      }
-      mx = std::max<uint64_t>(mx, j - b + 1);
-    }
-    return mx;
-  };
-  uint64_t T = conv_blk_tmax();
-  while (T > 512 && max_overlap(T) > kBlkCap) T /= 2;
-  if (max_overlap(T) > kBlkCap) return nullptr;
-  // span PACK (k_pack_blk_span): monotonic blocks; the user span of a
-  // T-byte stretch that starts in block b and ends in block j is
-  // T + G(j) - G(b), G = user offset - stream offset (non-decreasing), so
-  // its maximum over stretches starting in b is at the last j reachable
-  bool mono = true;
-  for (uint64_t b = 0; b + 1 < nb && mono; b++) mono = v[b].uoff + (int64_t)v[b].len <= v[b + 1].uoff;
-  mono = mono && v[nb - 1].uoff + (int64_t)v[nb - 1].len <= v[0].uoff + ext;
-  uint64_t Ts = 0, caps = 0;
-  if (mono && conv_blk_span()) {
-    auto G = [&](uint64_t j) {
-      const uint64_t i = j / nb;
-      return ((int64_t)i * ext + v[j - i * nb].uoff) - (int64_t)(i * S + v[j - i * nb].soff);
-    };
-    auto max_span = [&](uint64_t TT) {
-      int64_t mx = 0;
-      uint64_t j = 0;
-      for (uint64_t b = 0; b < nb; b++) {
-        const uint64_t last = (uint64_t)v[b].soff + v[b].len - 1 + TT - 1;
-        if (j < b) j = b;
-        while (true) {
-          const uint64_t jn = j + 1, i = jn / nb;
-          if (i * S + v[jn - i * nb].soff > last) break;
-          j = jn;
-        }
-        mx = std::max<int64_t>(mx, G(j) - G(b));
-      }
-      return (int64_t)TT + mx;
-    };
-    for (uint64_t TT = 16384; TT >= 2048; TT /= 2) {
-      if (max_overlap(TT) <= kBlkCap && max_span(TT) + 32 <= (int64_t)kBlkSpan) {
-        Ts = TT;
-        caps = max_overlap(TT) + 1;
-        break;
-      }
-    }
-  }
-  const uint64_t nk = (S + kBlkG - 1) / kBlkG;
-  std::vector<uint32_t> tf(nk + 1);
-  for (uint64_t k = 0, b = 0; k < nk; k++) {
-    while (b + 1 < nb && v[b + 1].soff <= k * kBlkG) b++;
-    tf[k] = (uint32_t)b;
-  }
-  tf[nk] = (uint32_t)(nb - 1);
-  std::vector<DBlk> dv(nb + 1);
-  for (uint64_t b = 0; b < nb; b++) {
-    if (v[b].uoff < INT32_MIN || v[b].uoff > INT32_MAX) return nullptr;   // instance offsets beyond +-2 GiB
-    dv[b].uoff = (int32_t)v[b].uoff;
-    dv[b].soff = v[b].soff;
-  }
-  dv[nb].uoff = 0;
-  dv[nb].soff = (uint32_t)S;
-  if (hipMalloc((void **)&B.dev, (nb + 1) * sizeof(DBlk)) != hipSuccess) { B.dev = nullptr; return nullptr; }
-  if (hipMalloc((void **)&B.tfirst, (nk + 1) * sizeof(uint32_t)) != hipSuccess) {
+  BlkPlan p;
+  if (!plan_blocks(d->lay, conv_env().blk_tmax, conv_env().blk_span, p)) return nullptr;
+  const size_t nd = p.dev.size() * sizeof(DBlk), nt = p.tfirst.size() * sizeof(uint32_t);
+  if (hipMalloc((void **)&B.dev, nd) != hipSuccess) { B.dev = nullptr; return nullptr; }
+  if (hipMalloc((void **)&B.tfirst, nt) != hipSuccess) {
     release_later(B.dev, REL_DEV);
     B.dev = nullptr;
     B.tfirst = nullptr;
     return nullptr;
   }
-  if (hipMemcpy(B.dev, dv.data(), (nb + 1) * sizeof(DBlk), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(B.tfirst, tf.data(), (nk + 1) * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
+  if (hipMemcpy(B.dev, p.dev.data(), nd, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(B.tfirst, p.tfirst.data(), nt, hipMemcpyHostToDevice) != hipSuccess) {
     release_later(B.dev, REL_DEV);
     release_later(B.tfirst, REL_DEV);
     B.dev = nullptr;
     B.tfirst = nullptr;
     return nullptr;
   }
-  B.host.swap(v);
-  B.T = T;
-  B.Tspan = Ts;
-  B.capspan = (uint32_t)caps;
+  B.host.swap(p.blocks);
+  B.T = p.T;
+  B.Tspan = p.Tspan;
+  B.capspan = p.capspan;
   B.built = 1;
   return &B;
-}
-
-// index of the piece holding packed byte b of an instance
-static uint32_t piece_of(const std::vector<DPiece> &v, uint64_t b) {
-  uint32_t lo = 0, hi = (uint32_t)v.size() - 1;
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi + 1) / 2;
-    if (v[mid].soff <= b) lo = mid; else hi = mid - 1;
-  }
-  return lo;
 }
 
 }  // namespace
@@ -2370,51 +2106,29 @@ static uint32_t piece_of(const std::vector<DPiece> &v, uint64_t b) {
 extern "C" int mx_ddt_create(const void *desc, size_t nrec, const uint64_t *basic_sizes, size_t size, int64_t lb,
                              int64_t ub, mx_ddt_t **out) {
   if (!desc || !nrec || !out) return MX_ERR_ARG;
-  const uint64_t *bs = basic_sizes ? basic_sizes : kBasicLP64;
   mx_ddt *d = new (std::nothrow) mx_ddt();
   if (!d) return MX_ERR_NOMEM;
-  int rc = flatten((const uint8_t *)desc, 0, nrec, 0, bs, d->host);
+  DdtLayout &L = d->lay;
+  int rc = ddt_layout_create(desc, nrec, basic_sizes, size, lb, ub, conv_env().bmap_inst, L);
   if (rc) { delete d; return rc; }
-  uint64_t poff = 0, g = 16;
-  for (DRun &r : d->host) {
-    r.poff = poff;
-    poff += r.bytes;
-    g = gcd64(g, absg(r.disp));
-    g = gcd64(g, r.blen);
-    if (r.cnt1 > 1) g = gcd64(g, absg(r.stride1));
-    if (r.cnt2 > 1) g = gcd64(g, absg(r.stride2));
-  }
-  if (poff != size) { delete d; return MX_ERR_ARG; }   // description / size mismatch
-  for (DRun &r : d->host) {
-    r.mblen = make_magic(r.blen);
-    r.mcnt1 = make_magic(r.cnt1);
-  }
-  d->size = size;
-  d->lb = lb;
-  d->ub = ub;
-  d->gcd_all = gcd64(g, absg(ub - lb));
-  d->mS = make_magic(size ? size : 1);
-  d->monotonic = is_monotonic(d->host, ub - lb);
-  d->dev = nullptr;
-  if (!d->host.empty()) {
+  if (!L.runs.empty()) {
     if ((rc = mx_ensure_init())) { delete d; return rc; }
-    if (hipMalloc((void **)&d->dev, d->host.size() * sizeof(DRun)) != hipSuccess ||
-        hipMemcpy(d->dev, d->host.data(), d->host.size() * sizeof(DRun), hipMemcpyHostToDevice) != hipSuccess) {
+    if (hipMalloc((void **)&d->dev, L.runs.size() * sizeof(DRun)) != hipSuccess ||
+        hipMemcpy(d->dev, L.runs.data(), L.runs.size() * sizeof(DRun), hipMemcpyHostToDevice) != hipSuccess) {
       if (d->dev) release_later(d->dev, REL_DEV);
       delete d;
       return MX_ERR_HIP;
     }
   }
-  build_bmap(d);
-  if (d->bmap_T) {
+  if (L.bmap_T) {
     std::vector<uint16_t> m16;
     std::vector<uint32_t> m32;
-    for (int32_t u : d->bmap) {
-      if (d->map16) m16.push_back((uint16_t)(u - d->umin));
-      else m32.push_back((uint32_t)(u - d->umin));
+    for (int32_t u : L.bmap) {
+      if (L.map16) m16.push_back((uint16_t)(u - L.umin));
+      else m32.push_back((uint32_t)(u - L.umin));
     }
-    const size_t nb = d->map16 ? m16.size() * 2 : m32.size() * 4;
-    const void *src = d->map16 ? (const void *)m16.data() : (const void *)m32.data();
+    const size_t nb = L.map16 ? m16.size() * 2 : m32.size() * 4;
+    const void *src = L.map16 ? (const void *)m16.data() : (const void *)m32.data();
     if (hipMalloc(&d->map_dev, nb) != hipSuccess || hipMemcpy(d->map_dev, src, nb, hipMemcpyHostToDevice) != hipSuccess) {
       if (d->map_dev) release_later(d->map_dev, REL_DEV);
       if (d->dev) release_later(d->dev, REL_DEV);
@@ -2441,157 +2155,271 @@ extern "C" int mx_ddt_destroy(mx_ddt_t *d) {
   return MX_SUCCESS;
 }
 
-extern "C" size_t mx_ddt_size(const mx_ddt_t *d) { return d ? d->size : 0; }
-extern "C" int64_t mx_ddt_extent(const mx_ddt_t *d) { return d ? d->ub - d->lb : 0; }
-extern "C" size_t mx_ddt_runs(const mx_ddt_t *d) { return d ? d->host.size() : 0; }
+extern "C" size_t mx_ddt_size(const mx_ddt_t *d) { return d ? d->lay.size : 0; }
+extern "C" int64_t mx_ddt_extent(const mx_ddt_t *d) { return d ? d->lay.ub - d->lay.lb : 0; }
+extern "C" size_t mx_ddt_runs(const mx_ddt_t *d) { return d ? d->lay.runs.size() : 0; }
 
 // Byte range [*lo, *hi) relative to `user` that `count` instances touch
 // (the true extent; instance i is displaced by i * extent).
 extern "C" int mx_ddt_span(const mx_ddt_t *d, size_t count, int64_t *lo, int64_t *hi) {
   if (!d || !lo || !hi) return MX_ERR_ARG;
-  *lo = *hi = 0;
-  if (!count || d->host.empty()) return MX_SUCCESS;
-  int64_t a = INT64_MAX, b = INT64_MIN;
-  for (const DRun &r : d->host) {
-    if (!r.bytes) continue;
-    const int64_t s1 = (int64_t)(r.cnt1 - 1) * r.stride1, s2 = (int64_t)(r.cnt2 - 1) * r.stride2;
-    const int64_t first = r.disp + std::min<int64_t>(0, s1) + std::min<int64_t>(0, s2);
-    const int64_t last = r.disp + std::max<int64_t>(0, s1) + std::max<int64_t>(0, s2) + (int64_t)r.blen;
-    a = std::min(a, first);
-    b = std::max(b, last);
-  }
-  if (a > b) return MX_SUCCESS;
-  const int64_t ext = d->ub - d->lb, tail = (int64_t)(count - 1) * ext;
-  *lo = a + std::min<int64_t>(0, tail);
-  *hi = b + std::max<int64_t>(0, tail);
+  ddt_span(d->lay, count, lo, hi);
   return MX_SUCCESS;
 }
 
-// MX_CONV_VEC=0 sends single-run layouts to the general kernels instead
-// (A/B measurement switch; results are identical).
-static bool conv_vec_enabled() { static const bool v = env_default_on("MX_CONV_VEC"); return v; }
+extern "C" int mx_ddt_last_path(const mx_ddt_t *d) { return d ? d->last_path.load(std::memory_order_relaxed) : PATH_NONE; }
 
-// MX_CONV_PIPE=0 sends PACK to the one-tile-per-workgroup kernel instead
-// of the pipelined one (A/B switch; results are identical).
-static bool conv_pipe_enabled() { static const bool v = env_default_on("MX_CONV_PIPE"); return v; }
+// ---------------------------------------------------------------------------
+// mx_pack / mx_unpack: one launcher per kernel family.  Each decides whether
+// the call is its own, fills its kernel's arguments, sizes the grid and
+// launches; it returns the call's result, or kPass for convert<PACK>() to
+// ask the next one.
+// ---------------------------------------------------------------------------
+namespace {
 
-// MX_CONV_BMAP=0 keeps small irregular instances on the run-walking tile
-// kernels (A/B switch; results are identical).
-static bool conv_bmap_enabled() { static const bool v = env_default_on("MX_CONV_BMAP"); return v; }
+struct Call {
+  mx_ddt *d;
+  const ConvEnv &env;
+  hipStream_t s;
+  ConvArgs a;        // the layout and the window: user, packed, offset, len
+  uint64_t u;        // widest access unit of the call (convert<PACK>(); not set for the copy)
+};
 
-// MX_CONV_BMAP_PACK=0 sends PACK of small dense instances to the piece
-// kernel instead of the byte-map kernel (A/B switch).
-static bool conv_bmap_pack_enabled() { static const bool v = env_default_on("MX_CONV_BMAP_PACK"); return v; }
+constexpr int kPass = 1;   // "not mine" (results are MX_SUCCESS or negative)
 
-// MX_CONV_PPACK=0 keeps PACK of layouts the byte map does not take on the
-// run-walking kernels instead of the piece kernel (A/B switch).
-static bool conv_ppack_enabled() { static const bool v = env_default_on("MX_CONV_PPACK"); return v; }
+void took(const Call &c, Path p) { c.d->last_path.store(p, std::memory_order_relaxed); }
 
-// MX_CONV_BMAP_DW=0 gives each lane of the byte-map PACK kernel 16 packed
-// bytes (one 16-byte store) instead of one dword per step (A/B switch).
-static bool conv_bmap_dw() { static const bool v = env_default_on("MX_CONV_BMAP_DW"); return v; }
+// x mod 16 as a gcd operand: 16 for a multiple of 16
+uint64_t res16(uint64_t x) { return x & 15 ? x & 15 : 16; }
 
-// MX_CONV_BLK: 0 keeps every layout off the BLOCK kernels, 1 (default)
-// sends instances without a byte map (> kBmapMaxS packed bytes) to them,
-// 2 also small instances (A/B against the byte-map / piece kernels; results
-// are identical).
-static int conv_blk_mode() {
-  static const int m = [] {
-    const char *e = getenv("MX_CONV_BLK");
-    const int v = e ? atoi(e) : 1;
-    return (v >= 0 && v <= 2) ? v : 1;
-  }();
-  return m;
+// workgroups per CU that `lds` bytes each leave room for (at most 8)
+uint64_t wgs_per_cu(size_t lds) { return std::max<uint64_t>(1, std::min<uint64_t>(8, (160 * 1024) / lds)); }
+
+// a persistent grid: one workgroup per tile up to per_cu resident on every CU
+unsigned tile_grid(uint64_t ntiles, uint64_t per_cu) {
+  return (unsigned)std::min<uint64_t>(ntiles, (uint64_t)g_num_cus * per_cu);
 }
 
-// MX_CONV_BMAP_PIPE=0 runs the byte-map PACK kernel without the span
-// prefetch of the next tile (A/B switch; results are identical).
-static bool conv_bmap_pipe() { static const bool v = env_default_on("MX_CONV_BMAP_PIPE"); return v; }
-
-// MX_CONV_BMAP_ALIGN=16|128: the byte-map PACK stages a tile's user span
-// from its first 16-byte granule or from the start of that granule's
-// 128-byte line, so that a wave's 1 KiB loads cover whole lines
-static uint64_t conv_bmap_align() {
-  static const uint64_t v = [] {
-    const char *e = getenv("MX_CONV_BMAP_ALIGN");
-    return (uint64_t)((e && atoi(e) == 16) ? 16 : 128);
-  }();
-  return v;
+// f(std::true_type) or f(std::false_type): a run-time flag as a template argument
+template <class F>
+void with_flag(bool b, F &&f) {
+  if (b) f(std::true_type());
+  else f(std::false_type());
 }
 
-// MX_CONV_BMAP_QUAD=0 stages the byte-map PACK's map as one row also where
-// S % 4 != 0 (A/B switch; results identical)
-static bool conv_bmap_quad() { static const bool v = env_default_on("MX_CONV_BMAP_QUAD"); return v; }
-
-// MX_CONV_BMAP_CW=0: the byte-map PACK reads every packed byte on its own
-// also where whole waves of packed dwords are user-contiguous (A/B switch)
-static bool conv_bmap_cw() { static const bool v = env_default_on("MX_CONV_BMAP_CW"); return v; }
-
-// MX_CONV_BMAP_NT=0: the byte-map PACK reads the user span and writes the
-// packed stream with ordinary accesses instead of non-temporal ones (A/B
-// switch).  The span is staged with one coalesced 16-byte load per lane, the
-// pattern whose floor is 1.23x faster non-temporal at 256 MiB
-// (tools/pack_floor_probe split-nt vs split-plain, profiles/r05/pack_floor_r5j.txt)
-static bool conv_bmap_nt() { static const bool v = env_default_on("MX_CONV_BMAP_NT"); return v; }
-
-// MX_CONV_VEC_NT=0: the VEC and VEC-span PACK kernels keep ordinary accesses
-// at the streaming sizes too (A/B switch)
-static bool conv_vec_nt() { static const bool v = env_default_on("MX_CONV_VEC_NT"); return v; }
-
-// MX_CONV_UNPACK_NTLD=1: the UNPACK kernels read the packed stream with
-// non-temporal loads at the streaming sizes (A/B switch, off: -5 % / +5 %
-// on indexed at 256 MiB / 1 GiB, within 1 % elsewhere, profiles/r05/conv_ab_r5y.txt;
-// the unpack is bound by its partial-line stores)
-static bool conv_unpack_ntld() { static const bool v = env_default_off("MX_CONV_UNPACK_NTLD"); return v; }
-
-// MX_CONV_UNPACK_U32=0: the piece UNPACK kernel's store loop in 64-bit
-// stream coordinates (round 4's form; A/B switch)
-static bool conv_unpack_u32() { static const bool v = env_default_on("MX_CONV_UNPACK_U32"); return v; }
-
-// MX_CONV_BMAP_WORD=1: the byte-map PACK stages a word map for word-piece
-// layouts (A/B switch, off: indexed 112 -> 137 us at 256 MiB with it, BLACS
-// equal, profiles/r05/conv_r5r.txt -- the gather gets shorter and the tile's
-// span prefetch, which it hid, is waited for instead)
-static bool conv_bmap_word() { static const bool v = env_default_off("MX_CONV_BMAP_WORD"); return v; }
-
-// MX_CONV_BMAP_UNROLL=0: one packed dword per lane per step in the byte-map
-// PACK's gather instead of kBmapU (A/B switch)
-static bool conv_bmap_unroll() { static const bool v = env_default_on("MX_CONV_BMAP_UNROLL"); return v; }
-
-// MX_CONV_BMAP_SPAN=12288|24576|49152: user span the byte-map PACK stages
-// per tile (A/B switch; the tile's stream bytes follow from it; unset: 24 KiB
-// where five workgroups fit a CU, else 12 KiB)
-static int conv_bmap_span_idx() {
-  static const int v = [] {
-    const char *e = getenv("MX_CONV_BMAP_SPAN");
-    if (!e) return -1;                                   // by the map's size
-    const long x = atol(e);
-    return x == kBmapSpans[0] ? 0 : x == kBmapSpans[2] ? 2 : 1;
-  }();
-  return v;
+// a contiguous type (one block, extent = size): the stream is the user
+// bytes themselves -- one copy (ref_contiguous_int2_77 unpack 2.27 TB/s
+// through the piece kernel)
+template <bool PACK>
+int launch_copy(const Call &c) {
+  const DdtLayout &L = c.d->lay;
+  const ConvArgs &a = c.a;
+  if (!(a.nruns == 1 && L.runs[0].cnt1 == 1 && L.runs[0].cnt2 == 1 && L.runs[0].blen == L.size &&
+        a.ext == (int64_t)L.size))
+    return kPass;
+  char *u = a.user + L.runs[0].disp + a.offset;
+  took(c, PATH_COPY);
+  return PACK ? copy_async(a.packed, u, a.len, c.s) : copy_async(u, a.packed, a.len, c.s);
 }
 
-// MX_CONV_UNPACK_PIPE=1 runs the piece UNPACK kernel with the register
-// prefetch of the next tile's packed range (A/B switch, off: measured
-// slower; results are identical).
-static bool conv_unpack_pipe() { static const bool v = env_default_off("MX_CONV_UNPACK_PIPE"); return v; }
+// periodic small blocks, PACK: whole 16-byte chunks of the span (k_pack_vec_span)
+int launch_vec_span(const Call &c) {
+  const DdtLayout &L = c.d->lay;
+  const ConvArgs &a = c.a;
+  if (!(a.nruns == 1 && L.runs[0].cnt2 == 1 && !c.d->force_blk && c.env.vec_span)) return kPass;
+  const DRun &R = L.runs[0];
+  // the period: the block stride, or the extent for one block per instance;
+  // instances continue it when extent == cnt1 * period, or the window stays
+  // inside instance 0 (one plain MPI vector)
+  const int64_t st = R.cnt1 > 1 ? R.stride1 : a.ext;
+  const char *ub = a.user + R.disp;
+  const bool periodic = (st == 8 || st == 16) && (int64_t)R.blen < st &&
+                        (a.ext == (int64_t)R.cnt1 * st || a.offset + a.len <= a.S) &&
+                        ((uintptr_t)ub & 15) == 0 && (R.blen == 4 || R.blen == 8) &&
+                        (((uintptr_t)a.packed - a.offset) & (16 / st * R.blen - 1)) == 0;
+  if (!periodic) return kPass;
+  const uint64_t outb = (uint64_t)(16 / st) * R.blen;   // packed bytes per chunk
+  const uint64_t q0 = a.offset / outb, q1 = (a.offset + a.len + outb - 1) / outb;
+  const uint64_t nq = q1 - q0;
+  const dim3 grid((unsigned)((nq + kCB - 1) / kCB)), block(kCB);
+  took(c, PATH_VEC);
+  // non-temporal at the streaming sizes (span + stream >= MX_NT_MIN_BYTES)
+  const bool nt = c.env.vec_nt && mx_nt_for((size_t)(a.len + a.len * (uint64_t)st / R.blen));
+  with_flag(nt, [&](auto NT) {
+    if (st == 8) hipLaunchKernelGGL((k_pack_vec_span<8, 4, NT()>), grid, block, 0, c.s, ub, a.packed, a.offset, a.len, q0, q1);
+    else if (R.blen == 8) hipLaunchKernelGGL((k_pack_vec_span<16, 8, NT()>), grid, block, 0, c.s, ub, a.packed, a.offset, a.len, q0, q1);
+    else hipLaunchKernelGGL((k_pack_vec_span<16, 4, NT()>), grid, block, 0, c.s, ub, a.packed, a.offset, a.len, q0, q1);
+  });
+  return mx_check_launch();
+}
 
-// The piece UNPACK form: MX_CONV_UNPACK_DIRECT=0 always the LDS-staged tile
-// kernel, =1 always one piece per lane, unset: measured per datatype
-// (mx_ddt::up_choice).  Results are identical.
-static int conv_unpack_direct() {
-  static const int v = [] {
-    const char *e = getenv("MX_CONV_UNPACK_DIRECT");
-    return (e && *e == '0') ? 1 : (e && *e == '1') ? 2 : 0;
-  }();
-  return v;
+// one strided 1-level run of whole aligned 4/8-byte words: the VEC kernel
+// (16-byte-granular layouts stay on k_convert<16>: measured 3.9 vs 2.8 TB/s
+// for 16-byte blocks at 1 GiB, while 4-byte blocks go 2.1 -> 3.5 TB/s here;
+// profiles/r01/convertor_vec_ab.txt)
+template <bool PACK>
+int launch_vec(const Call &c) {
+  const DdtLayout &L = c.d->lay;
+  const ConvArgs &a = c.a;
+  if (!(a.nruns == 1 && L.runs[0].cnt2 == 1 && c.u % 4 == 0 && c.u != 16 && L.runs[0].blen <= kVecMaxBlen &&
+        c.env.vec && !c.d->force_blk))
+    return kPass;
+  took(c, PATH_VEC);
+  const DRun &R = L.runs[0];
+  const uint64_t W = (c.u % 8 == 0) ? 8 : 4;
+  const uint64_t nw = a.len / W;
+  const dim3 grid((unsigned)((nw + kCB * kVIt - 1) / (kCB * kVIt))), block(kCB);
+  const float rblen = 1.0f / (float)R.blen;
+  // PACK: non-temporal at the streaming sizes (the user lines read + the
+  // stream written >= MX_NT_MIN_BYTES); UNPACK keeps cached stores (its
+  // partial-line writes)
+  const bool nt = PACK && c.env.vec_nt && mx_nt_for((size_t)(a.len + a.len * (uint64_t)R.stride1 / R.blen));
+  if (nt && W == 8) hipLaunchKernelGGL((k_convert_vec<8, PACK, true>), grid, block, 0, c.s, a, R, rblen);
+  else if (nt) hipLaunchKernelGGL((k_convert_vec<4, PACK, true>), grid, block, 0, c.s, a, R, rblen);
+  else if (W == 8) hipLaunchKernelGGL((k_convert_vec<8, PACK>), grid, block, 0, c.s, a, R, rblen);
+  else hipLaunchKernelGGL((k_convert_vec<4, PACK>), grid, block, 0, c.s, a, R, rblen);
+  return mx_check_launch();
+}
+
+// instances without a byte map (or every one, MX_CONV_BLK=2 /
+// MX_DDT_PATH_BLOCK) that the block table takes: the BLOCK kernels
+template <bool PACK>
+int launch_blk(const Call &c) {
+  mx_ddt *dm = c.d;
+  const ConvArgs &a = c.a;
+  const int blk = dm->force_blk ? 2 : c.env.blk_mode;
+  if (!(blk && (blk == 2 || dm->lay.bmap.empty()))) return kPass;
+  mx_ddt::BlkTab *bt;
+  {
+    std::lock_guard<std::mutex> g(dm->mu);
+    bt = blk_tab(dm);
+  }
+  if (!bt) return kPass;
+  BlkArgs b;
+  b.blk = bt->dev;
+  b.nblk = (uint32_t)bt->host.size();
+  b.mnblk = make_magic(b.nblk);
+  b.tfirst = bt->tfirst;
+  b.S = a.S;
+  b.mS = a.mS;
+  b.ext = a.ext;
+  b.user = a.user;
+  b.packed = a.packed;
+  b.offset = a.offset;
+  b.len = a.len;
+  b.T = bt->T;
+  const uintptr_t MA = (uintptr_t)a.packed & ~(uintptr_t)15;
+  b.ntiles = ((uintptr_t)a.packed + a.len - MA + b.T - 1) / b.T;
+  const unsigned grid = tile_grid(b.ntiles, 8);
+  took(c, PATH_BLOCK);
+  b.w4 = c.env.blk_w4;
+  if (PACK && bt->Tspan) {
+    b.T = bt->Tspan;
+    b.ntiles = ((uintptr_t)a.packed + a.len - MA + b.T - 1) / b.T;
+    const size_t lds = kBlkSpan + 32 + (size_t)bt->capspan * sizeof(SBlk) + (b.T / 64) * 2;
+    const unsigned gs = tile_grid(b.ntiles, wgs_per_cu(lds + 128));
+    hipLaunchKernelGGL(k_pack_blk_span, dim3(gs), dim3(kCB), lds, c.s, b, bt->capspan);
+    return mx_check_launch();
+  }
+  const int ng = c.env.blk_ng ? c.env.blk_ng : (PACK ? 2 : 4);
+  if (ng == 1) hipLaunchKernelGGL((k_convert_blk<PACK, 1>), dim3(grid), dim3(kCB), 0, c.s, b);
+  else if (ng == 2) hipLaunchKernelGGL((k_convert_blk<PACK, 2>), dim3(grid), dim3(kCB), 0, c.s, b);
+  else hipLaunchKernelGGL((k_convert_blk<PACK, 4>), dim3(grid), dim3(kCB), 0, c.s, b);
+  return mx_check_launch();
+}
+
+// the GRANULE kernel at unit U, the run table staged in LDS where it fits
+template <int U, bool PACK>
+void launch_convert_unit(const Call &c) {
+  const ConvArgs &a = c.a;
+  const size_t run_lds = a.nruns <= kLdsRuns ? (size_t)a.nruns * sizeof(DRun) : 0;
+  const dim3 grid((unsigned)(((a.len + 15) / 16 + kCB - 1) / kCB)), block(kCB);
+  if (run_lds) hipLaunchKernelGGL((k_convert<U, PACK, true>), grid, block, run_lds, c.s, a);
+  else hipLaunchKernelGGL((k_convert<U, PACK, false>), grid, block, 0, c.s, a);
+}
+
+// takes every call: whole 16-byte vectors (u == 16), and what no other
+// family took
+template <bool PACK>
+int launch_granule(const Call &c) {
+  took(c, PATH_GRANULE);
+  switch (c.u) {
+    case 16: launch_convert_unit<16, PACK>(c); break;
+    case 8: launch_convert_unit<8, PACK>(c); break;
+    case 4: launch_convert_unit<4, PACK>(c); break;
+    case 2: launch_convert_unit<2, PACK>(c); break;
+    default: launch_convert_unit<1, PACK>(c); break;
+  }
+  return mx_check_launch();
+}
+
+template <int SPAN, bool DW, bool PIPE, bool NT>
+void launch_bmap_map(bool map16, unsigned grid, size_t lds, hipStream_t s, const BmapArgs &b) {
+  if (map16) hipLaunchKernelGGL((k_pack_bmap<SPAN, uint16_t, DW, PIPE, NT>), dim3(grid), dim3(kCB), lds, s, b);
+  else hipLaunchKernelGGL((k_pack_bmap<SPAN, uint32_t, DW, PIPE, NT>), dim3(grid), dim3(kCB), lds, s, b);
+}
+
+// small irregular instances, PACK: the byte map (see the kernel)
+int launch_bmap(const Call &c) {
+  const DdtLayout &L = c.d->lay;
+  const ConvArgs &a = c.a;
+  const ConvEnv &E = c.env;
+  if (!(!L.bmap.empty() && E.bmap && L.bmap_T && !L.piece_pack && (((uintptr_t)a.packed - a.offset) & 15) == 0 &&
+        E.bmap_pack))
+    return kPass;
+  BmapArgs b;
+  b.map = c.d->map_dev;
+  b.mono = L.monotonic;
+  b.S = (uint32_t)L.size;
+  b.mS = L.mS;
+  b.ext = a.ext;
+  b.umin = L.umin;
+  b.uspan = L.uspan;
+  b.user = a.user;
+  b.packed = a.packed;
+  b.offset = a.offset;
+  b.len = a.len;
+  b.g0 = a.offset / 16;
+  const bool dw = E.bmap_dw, nt = E.bmap_nt, pipe = E.bmap_pipe;
+  int si = E.bmap_span_idx;
+  const bool word = L.bmap_word && E.bmap_word && dw;
+  const size_t map_lds = (word ? L.size / 4 : L.bmap_quad && E.bmap_quad ? 4 * L.size : L.size + 3) * (L.map16 ? 2 : 4);
+  // default: the 24 KiB span where five or more workgroups fit a CU (a
+  // small map), else 12 KiB, which keeps seven (indexed's 10 KiB map: four
+  // at 24 KiB).  On one box against the floors (profiles/r05/conv_ab_r5q.txt,
+  // pack_floor_r5q.txt), 256 MiB: struct 24 KiB 123 us / 12 KiB 159 /
+  // 48 KiB 157 (floor 125); indexed 123 / 116 / 180 (floor 109)
+  if (si < 0) si = wgs_per_cu(kBmapSpans[1] + 32 + map_lds + 128) >= 5 ? 1 : 0;
+  if (!L.bmap_Ts[si] || !(dw && nt && pipe) || kBmapSpans[si] + 32 + map_lds > 65536)
+    si = 1;                                       // other spans: the default kernel shape only
+  b.T = L.bmap_Ts[si];
+  b.ntiles = ((a.offset + a.len + 15) / 16 * 16 - b.g0 * 16 + b.T - 1) / b.T;
+  b.word = word;
+  b.qsh = !word && L.bmap_quad && E.bmap_quad ? 2 : 0;
+  b.cw = L.bmap_cw && E.bmap_cw;
+  b.unroll = E.bmap_unroll;
+  const size_t lds = kBmapSpans[si] + 32 + map_lds;
+  const unsigned grid = tile_grid(b.ntiles, wgs_per_cu(lds));
+  b.adv_b = (uint32_t)((kCB * 4) % L.size);
+  b.adv_io = (int64_t)((kCB * 4) / L.size) * b.ext;
+  b.lo_mask = E.bmap_align - 1;
+  took(c, PATH_BMAP);
+  if (si == 0) launch_bmap_map<kBmapSpans[0], true, true, true>(L.map16, grid, lds, c.s, b);
+  else if (si == 2) launch_bmap_map<kBmapSpans[2], true, true, true>(L.map16, grid, lds, c.s, b);
+  else
+    with_flag(dw, [&](auto DW) {
+      with_flag(pipe, [&](auto PIPE) {
+        with_flag(nt, [&](auto NT) { launch_bmap_map<kBmapSpan, DW(), PIPE(), NT()>(L.map16, grid, lds, c.s, b); });
+      });
+    });
+  return mx_check_launch();
 }
 
 // The form of this piece unpack (1 staged, 2 one piece per lane) and, during
 // the trials, the events to bracket it with (null otherwise).
-static int unpack_piece_form(mx_ddt *dm, uint64_t len, hipEvent_t *ev0, hipEvent_t *ev1) {
+int unpack_piece_form(mx_ddt *dm, uint64_t len, hipEvent_t *ev0, hipEvent_t *ev1) {
   *ev0 = *ev1 = nullptr;
-  if (const int f = conv_unpack_direct()) return f;
+  if (const int f = conv_env().unpack_direct) return f;
   std::lock_guard<std::mutex> lk(dm->up_mu);
   if (dm->up_choice) return dm->up_choice;
   if (len < ((uint64_t)4 << 20)) return 1;
@@ -2627,356 +2455,150 @@ static int unpack_piece_form(mx_ddt *dm, uint64_t len, hipEvent_t *ev0, hipEvent
   return dm->up_choice;
 }
 
-// MX_CONV_VEC_SPAN=0 packs periodic small-block vectors through the VEC
-// kernel instead of k_pack_vec_span (A/B switch; results are identical).
-static bool conv_vec_span() { static const bool v = env_default_on("MX_CONV_VEC_SPAN"); return v; }
-
-static int conv_pipe_geom() {
-  static const int g = [] {
-    const char *e = getenv("MX_CONV_PIPE_GEOM");
-    const int v = e ? atoi(e) : 0;
-    return (v >= 0 && v <= 3) ? v : 0;
-  }();
-  return g;
+// small irregular instances, UNPACK and the PACK the byte map leaves: the
+// piece kernels (see the kernels)
+template <bool PACK>
+int launch_piece(const Call &c) {
+  mx_ddt *dm = c.d;
+  const DdtLayout &L = dm->lay;
+  const ConvArgs &a = c.a;
+  if (!(!L.bmap.empty() && c.env.bmap && (!PACK || c.env.ppack))) return kPass;
+  mx_ddt::PieceTab *pt;
+  {
+    std::lock_guard<std::mutex> g(dm->mu);
+    pt = piece_tab(dm, (int)((uintptr_t)a.user & 15));
+  }
+  if (!pt) return kPass;
+  PieceArgs p;
+  const uint32_t npi = (uint32_t)pt->host.size();
+  p.pieces = pt->dev;
+  p.npi = npi;
+  p.mnpi = make_magic(npi);
+  p.S = L.size;
+  p.ext = a.ext;
+  p.user = a.user;
+  p.packed = a.packed;
+  p.offset = a.offset;
+  p.len = a.len;
+  const uint64_t i0 = a.offset / L.size, i1 = (a.offset + a.len - 1) / L.size;
+  p.P0 = i0 * npi + piece_of(pt->host, a.offset - i0 * L.size);
+  p.P1 = i1 * npi + piece_of(pt->host, a.offset + a.len - 1 - i1 * L.size) + 1;
+  p.K = pt->K;
+  p.dinst = (uint32_t)(kCB / npi);
+  p.dj = (uint32_t)(kCB % npi);
+  p.ntiles = (p.P1 - p.P0 + p.K - 1) / p.K;
+  p.tbl_lds = npi * sizeof(DPiece) <= 16384;
+  p.u32 = c.env.unpack_u32;
+  p.ntld = a.ntld;
+  const size_t lds = kPieceStage + 48 + (p.tbl_lds ? npi * sizeof(DPiece) : 0);
+  const unsigned grid = tile_grid(p.ntiles, wgs_per_cu(lds));
+  took(c, PATH_PIECE);
+  const uint64_t npieces = p.P1 - p.P0;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  const int form = PACK ? 1 : unpack_piece_form(dm, a.len, &ev0, &ev1);
+  if (ev0 && hipEventRecord(ev0, c.s) != hipSuccess) (void)hipGetLastError();
+  if (PACK) hipLaunchKernelGGL(k_pack_piece, dim3(grid), dim3(kCB), lds, c.s, p);
+  else if (form == 2 && npieces <= (uint64_t)UINT32_MAX * kCB) {
+    const unsigned g2 = (unsigned)((npieces + kCB - 1) / kCB);
+    if (p.ntld) hipLaunchKernelGGL(k_unpack_piece_direct<true>, dim3(g2), dim3(kCB), 0, c.s, p);
+    else hipLaunchKernelGGL(k_unpack_piece_direct<false>, dim3(g2), dim3(kCB), 0, c.s, p);
+  } else {
+    with_flag(c.env.unpack_pipe, [&](auto PIPE) {
+      with_flag(p.tbl_lds, [&](auto TL) {
+        hipLaunchKernelGGL((k_unpack_piece<PIPE(), TL()>), dim3(grid), dim3(kCB), lds, c.s, p);
+      });
+    });
+  }
+  const int lrc = mx_check_launch();
+  if (ev1 && hipEventRecord(ev1, c.s) != hipSuccess) (void)hipGetLastError();
+  return lrc;
 }
 
-// Tile size of the TILE kernels (MX_CONV_TP = 2048 / 4096 / 8192 for
-// measurement; results are identical).
-static int conv_tile_bytes() {
-  static const int tp = [] {
-    const char *e = getenv("MX_CONV_TP");
-    const int v = e ? atoi(e) : 0;
-    return (v == 2048 || v == 4096 || v == 8192) ? v : 8192;
-  }();
-  return tp;
+// the pipelined tile PACK at one geometry, wgs workgroups per CU
+template <int TP, int SPAN>
+void launch_pipe_geom(const Call &c, int nlds, size_t rb, int wgs) {
+  const uint64_t tiles = (c.a.len + TP - 1) / TP;
+  hipLaunchKernelGGL((k_pack_tile_pipe<TP, SPAN>), dim3(tile_grid(tiles, wgs)), dim3(kCB), (PipeGeom<TP, SPAN>::lds(rb)),
+                     c.s, c.a, nlds, tiles);
+}
+
+template <bool PACK, int TP>
+void launch_tile_bytes(const Call &c, int nlds, size_t rb, int wordpar) {
+  hipLaunchKernelGGL((k_convert_tile<PACK, TP>), dim3((unsigned)((c.a.len + TP - 1) / TP)), dim3(kCB),
+                     TileGeom<TP>::lds(PACK, rb), c.s, c.a, nlds, wordpar);
+}
+
+// narrow pieces: tile kernels (PACK needs a monotonic layout so that a
+// tile's user bytes form one span)
+template <bool PACK>
+int launch_tile(const Call &c) {
+  const DdtLayout &L = c.d->lay;
+  const ConvArgs &a = c.a;
+  if (!(!PACK || L.monotonic)) return kPass;
+  took(c, PATH_TILE);
+  const int nlds = a.nruns <= 64 ? 1 : 0;
+  const size_t rb = nlds ? (size_t)a.nruns * sizeof(DRun) : 0;
+  if (PACK && c.env.pipe) {
+    const int geom = c.env.pipe_geom;
+    if (geom == 2) launch_pipe_geom<9216, 28672>(c, nlds, rb, 3);
+    else if (geom == 3) launch_pipe_geom<8192, 16384>(c, nlds, rb, 6);
+    else if (geom == 1) launch_pipe_geom<9216, 16384>(c, nlds, rb, 6);
+    else launch_pipe_geom<8192, 24576>(c, nlds, rb, 4);
+    return mx_check_launch();
+  }
+  const int tp = c.env.tile_bytes;
+  // narrow 4-byte-aligned blocks: word-parallel stores (see the kernel)
+  uint64_t maxblen = 0;
+  for (const DRun &r : L.runs) maxblen = std::max<uint64_t>(maxblen, r.blen);
+  const int wordpar = !PACK && (c.u % 4) == 0 && maxblen <= 32;
+  if (tp == 2048) launch_tile_bytes<PACK, 2048>(c, nlds, rb, wordpar);
+  else if (tp == 4096) launch_tile_bytes<PACK, 4096>(c, nlds, rb, wordpar);
+  else launch_tile_bytes<PACK, 8192>(c, nlds, rb, wordpar);
+  return mx_check_launch();
 }
 
 template <bool PACK>
-static int convert(const mx_ddt_t *d, size_t count, char *user, char *packed, size_t offset, size_t len,
-                   void *stream) {
+int convert(const mx_ddt_t *d, size_t count, char *user, char *packed, size_t offset, size_t len, void *stream) {
   if (!d || !user || !packed) return MX_ERR_ARG;
   if (len == 0) return MX_SUCCESS;
-  if (d->size == 0 || offset + len > d->size * count) return MX_ERR_ARG;
+  const DdtLayout &L = d->lay;
+  if (L.size == 0 || offset + len > L.size * count) return MX_ERR_ARG;
   if ((offset + len) >> kMagicBits) return MX_ERR_UNSUPPORTED;   // > 256 TiB streams
   int rc = mx_ensure_init();
   if (rc) return rc;
-  ConvArgs a;
+  Call c = {const_cast<mx_ddt *>(d), conv_env(), (hipStream_t)stream, {}, 0};
+  ConvArgs &a = c.a;
   a.runs = d->dev;
-  a.nruns = (int)d->host.size();
-  a.S = d->size;
-  a.mS = d->mS;
-  a.ext = d->ub - d->lb;
+  a.nruns = (int)L.runs.size();
+  a.S = L.size;
+  a.mS = L.mS;
+  a.ext = L.ub - L.lb;
   a.user = user;
   a.packed = packed;
   a.offset = offset;
   a.len = len;
   a.pk_vec = ((uintptr_t)packed & 15) == 0;
-  a.ntld = !PACK && conv_unpack_ntld() && mx_nt_for((size_t)(2 * len));
-  hipStream_t s = (hipStream_t)stream;
-  mx_ddt *dm = const_cast<mx_ddt *>(d);
-  // a contiguous type (one block, extent = size): the stream is the user
-  // bytes themselves -- one copy (ref_contiguous_int2_77 unpack 2.27 TB/s
-  // through the piece kernel)
-  if (a.nruns == 1 && d->host[0].cnt1 == 1 && d->host[0].cnt2 == 1 && d->host[0].blen == d->size &&
-      a.ext == (int64_t)d->size) {
-    char *u = user + d->host[0].disp + offset;
-    dm->last_path.store(1, std::memory_order_relaxed);
-    return PACK ? copy_async(packed, u, len, s) : copy_async(u, packed, len, s);
-  }
+  a.ntld = !PACK && c.env.unpack_ntld && mx_nt_for((size_t)(2 * len));
+  rc = launch_copy<PACK>(c);
+  if (rc != kPass) return rc;
   // widest unit that every piece of every granule respects: layout gcd,
   // alignment of the user origin, and the stream offset of granule 0
-  uint64_t u = gcd64(d->gcd_all, ((uintptr_t)user) & 15 ? ((uintptr_t)user & 15) : 16);
-  u = gcd64(u, offset & 15 ? (offset & 15) : 16);
-  u = gcd64(u, len & 15 ? (len & 15) : 16);
-  if (!a.pk_vec) u = gcd64(u, (uintptr_t)packed & 15);
-  const size_t run_lds = a.nruns <= kLdsRuns ? (size_t)a.nruns * sizeof(DRun) : 0;
-  // periodic small blocks, PACK: whole 16-byte chunks of the span (k_pack_vec_span)
-  if (PACK && a.nruns == 1 && d->host[0].cnt2 == 1 && !d->force_blk && conv_vec_span()) {
-    const DRun &R = d->host[0];
-    // the period: the block stride, or the extent for one block per instance;
-    // instances continue it when extent == cnt1 * period, or the window stays
-    // inside instance 0 (one plain MPI vector)
-    const int64_t st = R.cnt1 > 1 ? R.stride1 : a.ext;
-    const char *ub = user + R.disp;
-    const bool periodic = (st == 8 || st == 16) && (int64_t)R.blen < st &&
-                          (a.ext == (int64_t)R.cnt1 * st || offset + len <= a.S) &&
-                          ((uintptr_t)ub & 15) == 0 && (R.blen == 4 || R.blen == 8) &&
-                          (((uintptr_t)packed - offset) & (16 / st * R.blen - 1)) == 0;
-    if (periodic) {
-      const uint64_t outb = (uint64_t)(16 / st) * R.blen;   // packed bytes per chunk
-      const uint64_t q0 = offset / outb, q1 = (offset + len + outb - 1) / outb;
-      const uint64_t nq = q1 - q0;
-      const dim3 grid((unsigned)((nq + kCB - 1) / kCB)), block(kCB);
-      dm->last_path.store(2, std::memory_order_relaxed);
-      // non-temporal at the streaming sizes (span + stream >= MX_NT_MIN_BYTES)
-      const bool nt = conv_vec_nt() && mx_nt_for((size_t)(len + len * (uint64_t)st / R.blen));
-#define MX_VSPAN(S_, B_)                                                                                      \
-  do {                                                                                                        \
-    if (nt) hipLaunchKernelGGL((k_pack_vec_span<S_, B_, true>), grid, block, 0, s, ub, packed, offset, len, q0, q1); \
-    else hipLaunchKernelGGL((k_pack_vec_span<S_, B_, false>), grid, block, 0, s, ub, packed, offset, len, q0, q1);   \
-  } while (0)
-      if (st == 8) MX_VSPAN(8, 4);
-      else if (R.blen == 8) MX_VSPAN(16, 8);
-      else MX_VSPAN(16, 4);
-#undef MX_VSPAN
-      return mx_check_launch();
-    }
-  }
-  // one strided 1-level run of whole aligned 4/8-byte words: the VEC kernel
-  // (16-byte-granular layouts stay on k_convert<16>: measured 3.9 vs 2.8 TB/s
-  // for 16-byte blocks at 1 GiB, while 4-byte blocks go 2.1 -> 3.5 TB/s here;
-  // profiles/r01/convertor_vec_ab.txt)
-  if (a.nruns == 1 && d->host[0].cnt2 == 1 && u % 4 == 0 && u != 16 && d->host[0].blen <= kVecMaxBlen &&
-      conv_vec_enabled() && !d->force_blk) {
-    dm->last_path.store(2, std::memory_order_relaxed);
-    const DRun &R = d->host[0];
-    const uint64_t W = (u % 8 == 0) ? 8 : 4;
-    const uint64_t nw = len / W;
-    const dim3 grid((unsigned)((nw + kCB * kVIt - 1) / (kCB * kVIt))), block(kCB);
-    const float rblen = 1.0f / (float)R.blen;
-    // PACK: non-temporal at the streaming sizes (the user lines read + the
-    // stream written >= MX_NT_MIN_BYTES); UNPACK keeps cached stores (its
-    // partial-line writes)
-    const bool nt = PACK && conv_vec_nt() && mx_nt_for((size_t)(len + len * (uint64_t)R.stride1 / R.blen));
-    if (nt && W == 8) hipLaunchKernelGGL((k_convert_vec<8, PACK, true>), grid, block, 0, s, a, R, rblen);
-    else if (nt) hipLaunchKernelGGL((k_convert_vec<4, PACK, true>), grid, block, 0, s, a, R, rblen);
-    else if (W == 8) hipLaunchKernelGGL((k_convert_vec<8, PACK>), grid, block, 0, s, a, R, rblen);
-    else hipLaunchKernelGGL((k_convert_vec<4, PACK>), grid, block, 0, s, a, R, rblen);
-    return mx_check_launch();
-  }
-  const int blk = d->force_blk ? 2 : conv_blk_mode();
-  if (blk && (blk == 2 || d->bmap.empty())) {
-    mx_ddt::BlkTab *bt;
-    {
-      std::lock_guard<std::mutex> g(dm->mu);
-      bt = blk_tab(dm);
-    }
-    if (bt) {
-      BlkArgs b;
-      b.blk = bt->dev;
-      b.nblk = (uint32_t)bt->host.size();
-      b.mnblk = make_magic(b.nblk);
-      b.tfirst = bt->tfirst;
-      b.S = d->size;
-      b.mS = d->mS;
-      b.ext = d->ub - d->lb;
-      b.user = user;
-      b.packed = packed;
-      b.offset = offset;
-      b.len = len;
-      b.T = bt->T;
-      const uintptr_t MA = (uintptr_t)packed & ~(uintptr_t)15;
-      b.ntiles = ((uintptr_t)packed + len - MA + b.T - 1) / b.T;
-      const uint64_t grid = std::min<uint64_t>(b.ntiles, (uint64_t)g_num_cus * 8);
-      dm->last_path.store(6, std::memory_order_relaxed);
-      b.w4 = conv_blk_w4();
-      if (PACK && bt->Tspan) {
-        b.T = bt->Tspan;
-        b.ntiles = ((uintptr_t)packed + len - MA + b.T - 1) / b.T;
-        const size_t lds = kBlkSpan + 32 + (size_t)bt->capspan * sizeof(SBlk) + (b.T / 64) * 2;
-        const uint64_t per_cu = std::max<uint64_t>(1, std::min<uint64_t>(8, (160 * 1024) / (lds + 128)));
-        const uint64_t gs = std::min<uint64_t>(b.ntiles, (uint64_t)g_num_cus * per_cu);
-        hipLaunchKernelGGL(k_pack_blk_span, dim3((unsigned)gs), dim3(kCB), lds, s, b, bt->capspan);
-        return mx_check_launch();
-      }
-      const int ng = conv_blk_ng(PACK);
-      if (ng == 1) hipLaunchKernelGGL((k_convert_blk<PACK, 1>), dim3((unsigned)grid), dim3(kCB), 0, s, b);
-      else if (ng == 2) hipLaunchKernelGGL((k_convert_blk<PACK, 2>), dim3((unsigned)grid), dim3(kCB), 0, s, b);
-      else hipLaunchKernelGGL((k_convert_blk<PACK, 4>), dim3((unsigned)grid), dim3(kCB), 0, s, b);
-      return mx_check_launch();
-    }
-  }
-  if (u == 16) {
-    dm->last_path.store(3, std::memory_order_relaxed);
-    const uint64_t g = (len + 15) / 16;
-    if (run_lds) hipLaunchKernelGGL((k_convert<16, PACK, true>), dim3((unsigned)((g + kCB - 1) / kCB)), dim3(kCB), run_lds, s, a);
-    else hipLaunchKernelGGL((k_convert<16, PACK, false>), dim3((unsigned)((g + kCB - 1) / kCB)), dim3(kCB), 0, s, a);
-    return mx_check_launch();
-  }
-  // small irregular instances: byte-map PACK / piece UNPACK (see the kernels)
-  if (!d->bmap.empty() && conv_bmap_enabled()) {
-    if (PACK && d->bmap_T && !d->piece_pack && (((uintptr_t)packed - offset) & 15) == 0 &&
-        conv_bmap_pack_enabled()) {
-      BmapArgs b;
-      b.map = d->map_dev;
-      b.mono = d->monotonic;
-      b.S = (uint32_t)d->size;
-      b.mS = d->mS;
-      b.ext = d->ub - d->lb;
-      b.umin = d->umin;
-      b.uspan = d->uspan;
-      b.user = user;
-      b.packed = packed;
-      b.offset = offset;
-      b.len = len;
-      b.g0 = offset / 16;
-      const bool dw = conv_bmap_dw(), nt = conv_bmap_nt(), pipe = conv_bmap_pipe();
-      int si = conv_bmap_span_idx();
-      const bool word = d->bmap_word && conv_bmap_word() && dw;
-      const size_t map_lds = (word ? d->size / 4 : d->bmap_quad && conv_bmap_quad() ? 4 * d->size : d->size + 3) *
-                             (d->map16 ? 2 : 4);
-      // default: the 24 KiB span where five or more workgroups fit a CU (a
-      // small map), else 12 KiB, which keeps seven (indexed's 10 KiB map: four
-      // at 24 KiB).  On one box against the floors (profiles/r05/conv_ab_r5q.txt,
-      // pack_floor_r5q.txt), 256 MiB: struct 24 KiB 123 us / 12 KiB 159 /
-      // 48 KiB 157 (floor 125); indexed 123 / 116 / 180 (floor 109)
-      if (si < 0) si = (160 * 1024) / (kBmapSpans[1] + 32 + map_lds + 128) >= 5 ? 1 : 0;
-      if (!d->bmap_Ts[si] || !(dw && nt && pipe) || kBmapSpans[si] + 32 + map_lds > 65536)
-        si = 1;                                       // other spans: the default kernel shape only
-      b.T = d->bmap_Ts[si];
-      b.ntiles = ((offset + len + 15) / 16 * 16 - b.g0 * 16 + b.T - 1) / b.T;
-      b.word = word;
-      b.qsh = !word && d->bmap_quad && conv_bmap_quad() ? 2 : 0;
-      b.cw = d->bmap_cw && conv_bmap_cw();
-      b.unroll = conv_bmap_unroll();
-      const size_t lds = kBmapSpans[si] + 32 + map_lds;
-      const uint64_t per_cu = std::max<uint64_t>(1, std::min<uint64_t>(8, (160 * 1024) / lds));
-      const uint64_t grid = std::min<uint64_t>(b.ntiles, (uint64_t)g_num_cus * per_cu);
-      b.adv_b = (uint32_t)((kCB * 4) % d->size);
-      b.adv_io = (int64_t)((kCB * 4) / d->size) * b.ext;
-      b.lo_mask = conv_bmap_align() - 1;
-      dm->last_path.store(4, std::memory_order_relaxed);
-      if (si != 1) {
-        if (d->map16) {
-          if (si == 0) hipLaunchKernelGGL((k_pack_bmap<kBmapSpans[0], uint16_t, true, true, true>), dim3((unsigned)grid), dim3(kCB), lds, s, b);
-          else hipLaunchKernelGGL((k_pack_bmap<kBmapSpans[2], uint16_t, true, true, true>), dim3((unsigned)grid), dim3(kCB), lds, s, b);
-        } else {
-          if (si == 0) hipLaunchKernelGGL((k_pack_bmap<kBmapSpans[0], uint32_t, true, true, true>), dim3((unsigned)grid), dim3(kCB), lds, s, b);
-          else hipLaunchKernelGGL((k_pack_bmap<kBmapSpans[2], uint32_t, true, true, true>), dim3((unsigned)grid), dim3(kCB), lds, s, b);
-        }
-        return mx_check_launch();
-      }
-#define MX_BMAP_LAUNCH2(M, DW, NT)                                                                               \
-  do {                                                                                                           \
-    if (pipe)                                                                                                    \
-      hipLaunchKernelGGL((k_pack_bmap<kBmapSpan, M, DW, true, NT>), dim3((unsigned)grid), dim3(kCB), lds, s, b); \
-    else                                                                                                         \
-      hipLaunchKernelGGL((k_pack_bmap<kBmapSpan, M, DW, false, NT>), dim3((unsigned)grid), dim3(kCB), lds, s, b);\
-  } while (0)
-#define MX_BMAP_LAUNCH(M, DW)                                                                                   \
-  do {                                                                                                           \
-    if (nt) MX_BMAP_LAUNCH2(M, DW, true);                                                                        \
-    else MX_BMAP_LAUNCH2(M, DW, false);                                                                          \
-  } while (0)
-      if (d->map16) { if (dw) MX_BMAP_LAUNCH(uint16_t, true); else MX_BMAP_LAUNCH(uint16_t, false); }
-      else { if (dw) MX_BMAP_LAUNCH(uint32_t, true); else MX_BMAP_LAUNCH(uint32_t, false); }
-#undef MX_BMAP_LAUNCH
-#undef MX_BMAP_LAUNCH2
-      return mx_check_launch();
-    }
-    if (!PACK || conv_ppack_enabled()) {
-      mx_ddt::PieceTab *pt;
-      {
-        std::lock_guard<std::mutex> g(dm->mu);
-        pt = piece_tab(dm, (int)((uintptr_t)user & 15));
-      }
-      if (pt) {
-        PieceArgs p;
-        const uint32_t npi = (uint32_t)pt->host.size();
-        p.pieces = pt->dev;
-        p.npi = npi;
-        p.mnpi = make_magic(npi);
-        p.S = d->size;
-        p.ext = d->ub - d->lb;
-        p.user = user;
-        p.packed = packed;
-        p.offset = offset;
-        p.len = len;
-        const uint64_t i0 = offset / d->size, i1 = (offset + len - 1) / d->size;
-        p.P0 = i0 * npi + piece_of(pt->host, offset - i0 * d->size);
-        p.P1 = i1 * npi + piece_of(pt->host, offset + len - 1 - i1 * d->size) + 1;
-        p.K = pt->K;
-        p.dinst = (uint32_t)(kCB / npi);
-        p.dj = (uint32_t)(kCB % npi);
-        p.ntiles = (p.P1 - p.P0 + p.K - 1) / p.K;
-        p.tbl_lds = npi * sizeof(DPiece) <= 16384;
-        p.u32 = conv_unpack_u32();
-        p.ntld = !PACK && conv_unpack_ntld() && mx_nt_for((size_t)(2 * len));
-        const size_t lds = kPieceStage + 48 + (p.tbl_lds ? npi * sizeof(DPiece) : 0);
-        const uint64_t per_cu = std::max<uint64_t>(1, std::min<uint64_t>(8, (160 * 1024) / lds));
-        const uint64_t grid = std::min<uint64_t>(p.ntiles, (uint64_t)g_num_cus * per_cu);
-        dm->last_path.store(5, std::memory_order_relaxed);
-        const uint64_t npieces = p.P1 - p.P0;
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;
-        const int form = PACK ? 1 : unpack_piece_form(dm, len, &ev0, &ev1);
-        if (ev0 && hipEventRecord(ev0, s) != hipSuccess) (void)hipGetLastError();
-        if (PACK) hipLaunchKernelGGL(k_pack_piece, dim3((unsigned)grid), dim3(kCB), lds, s, p);
-        else if (form == 2 && npieces <= (uint64_t)UINT32_MAX * kCB) {
-          const unsigned g2 = (unsigned)((npieces + kCB - 1) / kCB);
-          if (p.ntld) hipLaunchKernelGGL(k_unpack_piece_direct<true>, dim3(g2), dim3(kCB), 0, s, p);
-          else hipLaunchKernelGGL(k_unpack_piece_direct<false>, dim3(g2), dim3(kCB), 0, s, p);
-        } else if (conv_unpack_pipe()) {
-          if (p.tbl_lds) hipLaunchKernelGGL((k_unpack_piece<true, true>), dim3((unsigned)grid), dim3(kCB), lds, s, p);
-          else hipLaunchKernelGGL((k_unpack_piece<true, false>), dim3((unsigned)grid), dim3(kCB), lds, s, p);
-        } else if (p.tbl_lds) {
-          hipLaunchKernelGGL((k_unpack_piece<false, true>), dim3((unsigned)grid), dim3(kCB), lds, s, p);
-        } else {
-          hipLaunchKernelGGL((k_unpack_piece<false, false>), dim3((unsigned)grid), dim3(kCB), lds, s, p);
-        }
-        const int lrc = mx_check_launch();
-        if (ev1 && hipEventRecord(ev1, s) != hipSuccess) (void)hipGetLastError();
-        return lrc;
-      }
-    }
-  }
-  // narrow pieces: tile kernels (PACK needs a monotonic layout so that a
-  // tile's user bytes form one span)
-  if (!PACK || d->monotonic) {
-    dm->last_path.store(7, std::memory_order_relaxed);
-    const int nlds = a.nruns <= 64 ? 1 : 0;
-    const size_t rb = nlds ? (size_t)a.nruns * sizeof(DRun) : 0;
-    if (PACK && conv_pipe_enabled()) {
-      // MX_CONV_PIPE_GEOM selects the tile geometry (A/B measurement; results
-      // are identical): 0 = 8192 x 24 KiB span, 1 = 9216 x 16 KiB,
-      // 2 = 9216 x 28 KiB, 3 = 8192 x 16 KiB.  0 is fastest on every type
-      // measured (profiles/r02/convertor_r2.txt): the bank-conflict-free
-      // 36-byte stretches of 1 / 2 lose more to the tile / occupancy change
-      // than the conflicts cost (20k of ~4M cycles per wave).
-      const int geom = conv_pipe_geom();
-#define MX_PIPE_LAUNCH(TPV, SPV, WGS)                                                                        \
-  do {                                                                                                        \
-    const uint64_t tiles = (len + TPV - 1) / TPV;                                                             \
-    const uint64_t grid = std::min<uint64_t>(tiles, (uint64_t)g_num_cus * (WGS));                             \
-    hipLaunchKernelGGL((k_pack_tile_pipe<TPV, SPV>), dim3((unsigned)grid), dim3(kCB),                          \
-                       (PipeGeom<TPV, SPV>::lds(rb)), s, a, nlds, tiles);                                        \
-  } while (0)
-      if (geom == 2) MX_PIPE_LAUNCH(9216, 28672, 3);
-      else if (geom == 3) MX_PIPE_LAUNCH(8192, 16384, 6);
-      else if (geom == 1) MX_PIPE_LAUNCH(9216, 16384, 6);
-      else MX_PIPE_LAUNCH(8192, 24576, 4);
-#undef MX_PIPE_LAUNCH
-      return mx_check_launch();
-    }
-    const int tp = conv_tile_bytes();
-    // narrow 4-byte-aligned blocks: word-parallel stores (see the kernel)
-    uint64_t maxblen = 0;
-    for (const DRun &r : d->host) maxblen = std::max<uint64_t>(maxblen, r.blen);
-    const int wordpar = !PACK && (u % 4) == 0 && maxblen <= 32;
-#define MX_TILE_LAUNCH(TPV)                                                                          \
-  hipLaunchKernelGGL((k_convert_tile<PACK, TPV>), dim3((unsigned)((len + TPV - 1) / TPV)), dim3(kCB),     \
-                     TileGeom<TPV>::lds(PACK, rb), s, a, nlds, wordpar)
-    if (tp == 2048) MX_TILE_LAUNCH(2048);
-    else if (tp == 4096) MX_TILE_LAUNCH(4096);
-    else MX_TILE_LAUNCH(8192);
-#undef MX_TILE_LAUNCH
-    return mx_check_launch();
-  }
-  const dim3 grid((unsigned)(((len + 15) / 16 + kCB - 1) / kCB)), block(kCB);
-  dm->last_path.store(3, std::memory_order_relaxed);
-#define MX_CONV_LAUNCH(U)                                                                   \
-  do {                                                                                      \
-    if (run_lds) hipLaunchKernelGGL((k_convert<U, PACK, true>), grid, block, run_lds, s, a); \
-    else hipLaunchKernelGGL((k_convert<U, PACK, false>), grid, block, 0, s, a);              \
-  } while (0)
-  switch (u) {
-    case 8: MX_CONV_LAUNCH(8); break;
-    case 4: MX_CONV_LAUNCH(4); break;
-    case 2: MX_CONV_LAUNCH(2); break;
-    default: MX_CONV_LAUNCH(1); break;
-  }
-#undef MX_CONV_LAUNCH
-  return mx_check_launch();
+  c.u = gcd64(L.gcd_all, res16((uintptr_t)user));
+  c.u = gcd64(c.u, res16(offset));
+  c.u = gcd64(c.u, res16(len));
+  if (!a.pk_vec) c.u = gcd64(c.u, (uintptr_t)packed & 15);
+  if (PACK) rc = launch_vec_span(c);
+  if (rc == kPass) rc = launch_vec<PACK>(c);
+  if (rc == kPass) rc = launch_blk<PACK>(c);
+  if (rc == kPass && c.u == 16) rc = launch_granule<PACK>(c);
+  if (rc == kPass && PACK) rc = launch_bmap(c);
+  if (rc == kPass) rc = launch_piece<PACK>(c);
+  if (rc == kPass) rc = launch_tile<PACK>(c);
+  if (rc == kPass) rc = launch_granule<PACK>(c);
+  return rc;
 }
+
+}  // namespace
 
 extern "C" int mx_ddt_set_path(mx_ddt_t *d, int path) {
   if (!d || (path != MX_DDT_PATH_AUTO && path != MX_DDT_PATH_BLOCK)) return MX_ERR_ARG;
@@ -2989,8 +2611,6 @@ extern "C" int mx_ddt_set_path(mx_ddt_t *d, int path) {
   d->force_blk = path == MX_DDT_PATH_BLOCK;
   return MX_SUCCESS;
 }
-
-extern "C" int mx_ddt_last_path(const mx_ddt_t *d) { return d ? d->last_path.load(std::memory_order_relaxed) : 0; }
 
 extern "C" int mx_pack(const mx_ddt_t *d, size_t count, const void *user, void *packed, size_t offset, size_t len,
                        void *stream) {
