@@ -103,7 +103,10 @@ enum {
     MX_TYPE_INTEGER4,
     MX_TYPE_INTEGER8,
     MX_TYPE_INTEGER16,        /* never built by the reference (no kernel) */
-    MX_TYPE_SHORT_FLOAT,      /* never built by the reference (no kernel) */
+    MX_TYPE_SHORT_FLOAT,      /* IEEE binary16 (2 B): MPIX_SHORT_FLOAT, built by the
+                                 reference where its host compiler has a 16-bit
+                                 float (HAVE_OPAL_SHORT_FLOAT_T); outside table
+                                 variants 0 and 1, see MX_TABLE_SHORT_FLOAT      */
     MX_TYPE_FLOAT,
     MX_TYPE_DOUBLE,
     MX_TYPE_REAL,             /* Fortran REAL      (4 B)                  */
@@ -115,7 +118,8 @@ enum {
     MX_TYPE_LONG_DOUBLE,      /* x87 80-bit in 16 B                       */
     MX_TYPE_LOGICAL,          /* Fortran LOGICAL   (4 B)                  */
     MX_TYPE_BOOL,
-    MX_TYPE_C_SHORT_FLOAT_COMPLEX, /* never built                         */
+    MX_TYPE_C_SHORT_FLOAT_COMPLEX, /* two binary16, real part first (4 B):
+                                 MPIX_C_SHORT_FLOAT_COMPLEX, as MX_TYPE_SHORT_FLOAT */
     MX_TYPE_C_FLOAT_COMPLEX,
     MX_TYPE_C_DOUBLE_COMPLEX,
     MX_TYPE_C_LONG_DOUBLE_COMPLEX,
@@ -138,6 +142,13 @@ enum {
  * with Fortran = 176 pairs. */
 #define MX_TABLE_C_ONLY      0
 #define MX_TABLE_WITH_FORTRAN 1
+/* A flag or-ed onto either variant: the reference's host compiler has a
+ * 16-bit float (HAVE_OPAL_SHORT_FLOAT_T and HAVE_OPAL_SHORT_FLOAT_COMPLEX_T),
+ * which adds SHORT_FLOAT x {MAX MIN SUM PROD} and C_SHORT_FLOAT_COMPLEX x
+ * {SUM PROD}: 122 and 182 pairs.  The kernels take the two slots whatever
+ * the variant (mx_reduce2/3, the collectives, mx_accumulate); the flag only
+ * selects what mx_op_supported and mx_type_size_ex report. */
+#define MX_TABLE_SHORT_FLOAT 2
 
 /* ---- runtime --------------------------------------------------------- */
 
@@ -192,6 +203,10 @@ const char *mx_version(void);
 /* Element size in bytes of a type slot (pair types include padding:
  * short_int 8, double_int 16, long_double_int 32 ...); 0 if none. */
 size_t mx_type_size(int type);
+/* As mx_type_size for the given table variant: with MX_TABLE_SHORT_FLOAT
+ * the binary16 slots have sizes 2 and 4 (mx_type_size keeps them at 0, the
+ * reference configuration without a 16-bit float). */
+size_t mx_type_size_ex(int type, int table_variant);
 /* 1 if (op,type) has a kernel in the given table variant, else 0.  The
  * pattern equals the reference table's non-NULL pattern exactly. */
 int mx_op_supported(int op, int type, int table_variant);

@@ -1201,7 +1201,7 @@ extern "C" int mx_allreduce_local(mx_comm_t *c, const void *const *sbufs, void *
   if (!c || !c->local || !rbufs) return MX_ERR_ARG;
   fold_launch_fn fl = fold_fns(op, type).fold;
   if (!fl) return MX_ERR_UNSUPPORTED;
-  const size_t es = mx_type_size(type);
+  const size_t es = type_size(type);
   const int n = c->size;
   hipStream_t s = (hipStream_t)stream;
   if (int orc = order(c, s)) return orc;
@@ -1255,7 +1255,7 @@ extern "C" int mx_reduce_scatter_local(mx_comm_t *c, const void *const *sbufs, v
   if (!c || !c->local || !rbufs || !rcounts) return MX_ERR_ARG;
   fold_launch_fn fl = fold_fns(op, type).fold;
   if (!fl) return MX_ERR_UNSUPPORTED;
-  const size_t es = mx_type_size(type);
+  const size_t es = type_size(type);
   const int n = c->size;
   hipStream_t s = (hipStream_t)stream;
   if (int orc = order(c, s)) return orc;
@@ -1944,7 +1944,7 @@ extern "C" int mx_allreduce(mx_comm_t *c, const void *sbuf, void *rbuf, size_t c
   }
   hipStream_t s = (hipStream_t)stream;
   if (int orc = order(c, s)) return orc;
-  const size_t es = mx_type_size(type);
+  const size_t es = type_size(type);
   if (!es) return MX_ERR_ARG;
   const int n = c->size;
   const char *sb = (sbuf == MX_IN_PLACE || !sbuf) ? (const char *)rbuf : (const char *)sbuf;
@@ -2040,7 +2040,7 @@ static int reduce_scatter_impl(mx_comm_t *c, const void *sbuf, void *rbuf, const
   }
   hipStream_t s = (hipStream_t)stream;
   if (int orc = order(c, s)) return orc;
-  const size_t es = mx_type_size(type);
+  const size_t es = type_size(type);
   if (!es) return MX_ERR_ARG;
   const int n = c->size, r = c->rank;
   const char *sb = (sbuf == MX_IN_PLACE || !sbuf) ? (const char *)rbuf : (const char *)sbuf;
@@ -2219,7 +2219,7 @@ constexpr size_t kBcastDirectMax = 512 << 10;
 extern "C" int mx_reduce_scatter(mx_comm_t *c, const void *sbuf, void *rbuf, const size_t *rcounts, int type,
                                  int op, int alg, void *stream) {
   int bucket = -1, cand = -1;
-  const size_t es = mx_type_size(type);
+  const size_t es = type_size(type);
   if (c && !c->local && rcounts && es) {
     size_t total = 0;
     for (int j = 0; j < c->size; j++) total += rcounts[j];
@@ -2572,7 +2572,7 @@ static int vm_scatter_blocks(mx_comm *c, vm_launch_fn vl, const VmProg &p, const
 static int vm_setup(int op, int type, vm_launch_fn *vl, size_t *es) {
   *vl = fold_fns(op, type).vm;
   if (!*vl) return MX_ERR_UNSUPPORTED;
-  *es = mx_type_size(type);
+  *es = type_size(type);
   return *es ? MX_SUCCESS : MX_ERR_ARG;
 }
 
@@ -2880,7 +2880,7 @@ namespace {
 
 static int nbc_allreduce(mx_comm *c, const void *sbuf, void *rbuf, size_t count, int type, int op, int alg,
                          hipStream_t s) {
-  const size_t es = mx_type_size(type);
+  const size_t es = type_size(type);
   if (!es) return MX_ERR_ARG;
   const int n = c->size;
   const bool inplace = sbuf == MX_IN_PLACE || !sbuf || sbuf == rbuf;
@@ -3102,7 +3102,7 @@ static int req_reduction(mx_comm_t *c, int kind, int persistent, const void *sbu
   mx_request *q;
   int rc = req_new(c, kind, persistent, stream, req, &q);
   if (rc) return rc;
-  if (!mx_type_size(type) || (kind != RQ_REDUCE && !rbuf)) rc = MX_ERR_ARG;
+  if (!type_size(type) || (kind != RQ_REDUCE && !rbuf)) rc = MX_ERR_ARG;
   else if (!fold_fns(op, type).vm) rc = MX_ERR_UNSUPPORTED;
   if (rc) {
     req_event_put(q->done);
@@ -3176,7 +3176,7 @@ static int req_reduce_scatter(mx_comm_t *c, int kind, int persistent, const void
   mx_request *q;
   int rc = req_new(c, kind, persistent, stream, req, &q);
   if (rc) return rc;
-  if (!mx_type_size(type) || !rbuf) rc = MX_ERR_ARG;
+  if (!type_size(type) || !rbuf) rc = MX_ERR_ARG;
   else if (!fold_fns(op, type).vm) rc = MX_ERR_UNSUPPORTED;
   if (rc) {
     req_event_put(q->done);
@@ -3543,7 +3543,7 @@ extern "C" int mx_shmem_reduce(mx_comm_t *c, int sop, int st, size_t dt_size, vo
   int op, type;
   int rc = mx_shmem_to_mpi(sop, st, dt_size, &op, &type);
   if (rc) return rc;
-  if (!mx_op_supported(op, type, MX_TABLE_WITH_FORTRAN)) return MX_ERR_UNSUPPORTED;
+  if (!op_has_kernel(op, type)) return MX_ERR_UNSUPPORTED;
   if (nreduce == 0) return MX_SUCCESS;
   // scoll/mpi casts the count to int for coll_allreduce and falls back to
   // the previous scoll module above INT_MAX (scoll_mpi_ops.c:246-259)
@@ -3918,8 +3918,8 @@ extern "C" int mx_shmem_reduce_heap(mx_heap_t *h, int sop, int st, size_t dt_siz
   int rc = mx_shmem_to_mpi(sop, st, dt_size, &op, &type);
   if (rc) return rc;
   fold_launch_fn fl = fold_fns(op, type).fold;
-  if (!fl || !mx_op_supported(op, type, MX_TABLE_WITH_FORTRAN)) return MX_ERR_UNSUPPORTED;
-  const size_t es = mx_type_size(type);
+  if (!fl || !op_has_kernel(op, type)) return MX_ERR_UNSUPPORTED;
+  const size_t es = type_size(type);
   if (pe_size < 1 || pe_size > MAXR || pe_start < 0 || log_pe_stride < 0 || log_pe_stride > 5) return MX_ERR_ARG;
   int members[MAXR], me = -1;
   uint32_t mask = 0;
@@ -4053,14 +4053,14 @@ static int acc_unlock(mx_heap *h, int pe, hipStream_t s) {
 }
 
 static bool acc_op_ok(int op, int type) {
-  if (!mx_type_size(type)) return false;
-  return op == MX_OP_REPLACE || op == MX_OP_NO_OP || mx_op_supported(op, type, MX_TABLE_WITH_FORTRAN);
+  if (!type_size(type)) return false;
+  return op == MX_OP_REPLACE || op == MX_OP_NO_OP || op_has_kernel(op, type);
 }
 
 // target op= origin on `count` elements at `remote` (lock held)
 static int acc_apply(int op, int type, const void *origin, void *remote, size_t count, hipStream_t s) {
   if (op == MX_OP_NO_OP || !count) return MX_SUCCESS;
-  if (op == MX_OP_REPLACE) return copy_async(remote, origin, count * mx_type_size(type), s);
+  if (op == MX_OP_REPLACE) return copy_async(remote, origin, count * type_size(type), s);
   return mx_reduce2(op, type, origin, remote, count, s);
 }
 
@@ -4068,7 +4068,7 @@ static int acc_common(mx_heap *h, const void *origin, void *result, size_t count
                       void *target, void *stream) {
   if (!h || pe < 0 || pe >= h->c->size || !target) return MX_ERR_ARG;
   if (!acc_op_ok(op, type)) return MX_ERR_UNSUPPORTED;
-  const size_t es = mx_type_size(type);
+  const size_t es = type_size(type);
   if (!heap_has(h, target, count * es) || (!origin && op != MX_OP_NO_OP && count)) return MX_ERR_ARG;
   void *remote = mx_shmem_ptr(h, target, pe);
   if (!remote) return MX_ERR_ARG;
@@ -4104,7 +4104,7 @@ extern "C" int mx_fetch_and_op(mx_heap_t *h, const void *origin, void *result, i
 extern "C" int mx_compare_and_swap(mx_heap_t *h, const void *origin, const void *compare, void *result, int type,
                                    int pe, void *target, void *stream) {
   if (!h || !origin || !compare || !result || pe < 0 || pe >= h->c->size) return MX_ERR_ARG;
-  const size_t es = mx_type_size(type);
+  const size_t es = type_size(type);
   if (!es || !heap_has(h, target, es)) return MX_ERR_ARG;
   void *remote = mx_shmem_ptr(h, target, pe);
   hipStream_t s = (hipStream_t)stream;
@@ -4124,7 +4124,7 @@ extern "C" int mx_accumulate_ddt(mx_heap_t *h, const void *origin, size_t origin
                                  const mx_ddt_t *target_ddt, void *stream) {
   if (!h || pe < 0 || pe >= h->c->size || !target || (!origin && op != MX_OP_NO_OP)) return MX_ERR_ARG;
   if (!acc_op_ok(op, type)) return MX_ERR_UNSUPPORTED;
-  const size_t es = mx_type_size(type);
+  const size_t es = type_size(type);
   const size_t obytes = origin_ddt ? origin_count * mx_ddt_size(origin_ddt) : origin_count * es;
   const size_t tbytes = target_ddt ? target_count * mx_ddt_size(target_ddt) : target_count * es;
   if (obytes != tbytes || obytes % es) return MX_ERR_ARG;

@@ -5,7 +5,8 @@
 // (ompi/mca/op/base/op_base_functions.c:1485-1655): C integers x
 // {MAX MIN SUM PROD LAND LOR LXOR BAND BOR BXOR}; Fortran integers x
 // {MAX MIN SUM PROD BAND BOR BXOR}; float/double/long double (+ Fortran
-// reals) x {MAX MIN SUM PROD}; LOGICAL and bool x {LAND LOR LXOR}; complex x
+// reals, + binary16 where the reference's host has one) x {MAX MIN SUM
+// PROD}; LOGICAL and bool x {LAND LOR LXOR}; complex x
 // {SUM PROD}; BYTE x {BAND BOR BXOR}; pair types x {MAXLOC MINLOC}.
 //
 // A visitor V provides `template <class T, class OP2, class OP3> R go()` and
@@ -18,6 +19,7 @@
 
 namespace mx {
 
+using f16c = cplx<half>;
 using f32c = cplx<float>;
 using f64c = cplx<double>;
 using p_float_int = pair_t<float, int>;
@@ -60,7 +62,8 @@ __device__ __forceinline__ void store_fields(x87_pair *p, const x87_pair &r) {
 static_assert(sizeof(p_float_int) == 8 && sizeof(p_double_int) == 16 && sizeof(p_long_int) == 16 &&
               sizeof(p_2int) == 8 && sizeof(p_short_int) == 8 && sizeof(p_2real) == 8 &&
               sizeof(p_2double) == 16 && sizeof(x87_pair) == 32 && sizeof(f32c) == 8 &&
-              sizeof(f64c) == 16 && sizeof(x87) == 16 && sizeof(x87c) == 32,
+              sizeof(f64c) == 16 && sizeof(x87) == 16 && sizeof(x87c) == 32 && sizeof(half) == 2 &&
+              sizeof(f16c) == 4,
               "pair/complex layouts must match the host ABI");
 
 template <class T, class V> static auto d_int(int op, V &v) {
@@ -153,11 +156,13 @@ template <class V> static auto dispatch(int op, int type, V &v) {
     case MX_TYPE_INTEGER1: return d_fint<int8_t>(op, v);
     case MX_TYPE_INTEGER2: return d_fint<int16_t>(op, v);
     case MX_TYPE_INTEGER8: return d_fint<int64_t>(op, v);
+    case MX_TYPE_SHORT_FLOAT: return d_flt<half>(op, v);
     case MX_TYPE_FLOAT: case MX_TYPE_REAL: case MX_TYPE_REAL4: return d_flt<float>(op, v);
     case MX_TYPE_DOUBLE: case MX_TYPE_REAL8: case MX_TYPE_DOUBLE_PRECISION: return d_flt<double>(op, v);
     case MX_TYPE_LONG_DOUBLE: return d_x87(op, v);
     case MX_TYPE_LOGICAL: return d_logic<int32_t>(op, v);
     case MX_TYPE_BOOL: return d_logic<uint8_t>(op, v);
+    case MX_TYPE_C_SHORT_FLOAT_COMPLEX: return d_cplx<f16c>(op, v);
     case MX_TYPE_C_FLOAT_COMPLEX: return d_cplx<f32c>(op, v);
     case MX_TYPE_C_DOUBLE_COMPLEX: return d_cplx<f64c>(op, v);
     case MX_TYPE_C_LONG_DOUBLE_COMPLEX: return d_x87c(op, v);

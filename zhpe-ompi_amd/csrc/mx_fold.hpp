@@ -678,7 +678,8 @@ struct FoldFns {
 };
 
 // family of an element type: 0 8/16-bit integers, 1 32/64-bit integers,
-// 2 float / double / complex, 3 x87 long double (+ complex), 4 pair types
+// 2 float / double / complex, 3 x87 long double (+ complex), 4 pair types,
+// 5 binary16 (+ complex)
 template <class T> struct fam { static constexpr int value = sizeof(T) <= 2 ? 0 : 1; };
 template <> struct fam<float> { static constexpr int value = 2; };
 template <> struct fam<double> { static constexpr int value = 2; };
@@ -688,7 +689,9 @@ template <> struct fam<x87> { static constexpr int value = 3; };
 template <> struct fam<x87c> { static constexpr int value = 3; };
 template <class V, class K> struct fam<pair_t<V, K>> { static constexpr int value = 4; };
 template <> struct fam<x87_pair> { static constexpr int value = 4; };
-constexpr int NFAM = 5;
+template <> struct fam<half> { static constexpr int value = 5; };
+template <> struct fam<cplx<half>> { static constexpr int value = 5; };
+constexpr int NFAM = 6;
 
 template <int F>
 struct FamVisitor {
@@ -707,10 +710,11 @@ FoldFns fold_fns_fam1(int op, int type);
 FoldFns fold_fns_fam2(int op, int type);
 FoldFns fold_fns_fam3(int op, int type);
 FoldFns fold_fns_fam4(int op, int type);
+FoldFns fold_fns_fam5(int op, int type);
 
 inline FoldFns fold_fns(int op, int type) {
   FoldFns (*const f[NFAM])(int, int) = {fold_fns_fam0, fold_fns_fam1, fold_fns_fam2, fold_fns_fam3,
-                                         fold_fns_fam4};
+                                         fold_fns_fam4, fold_fns_fam5};
   for (int i = 0; i < NFAM; i++) {
     const FoldFns r = f[i](op, type);
     if (r.fold) return r;

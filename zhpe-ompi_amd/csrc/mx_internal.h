@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include "../../include/mx_kernels.h"
 #include "../../include/mx_rdma.h"
+#include "mx_slots.hpp"
 
 #include <vector>
 

@@ -17,11 +17,17 @@
 //  * complex PROD is the unfused (ac-bd, ad+bc) of GCC's inline expansion,
 //    with libgcc __mulsc3/__muldc3's Annex-G recovery when both parts are
 //    NaN; the library is compiled with -ffp-contract=off.
+//  * binary16 (MPIX_SHORT_FLOAT): one correctly rounded half operation per
+//    element, subnormals kept; its complex PROD is COMPLEX_PROD_FUNC
+//    (:132-147), six half operations and no Annex-G recovery.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace mx {
+
+// IEEE binary16: opal_short_float_t of a reference built with a 16-bit float
+using half = _Float16;
 
 template <class T> struct utype { using type = T; };
 template <> struct utype<int8_t> { using type = uint32_t; };
@@ -49,6 +55,7 @@ struct OpSum {
   }
   __device__ __forceinline__ float operator()(float x, float y) const { return __fadd_rn(x, y); }
   __device__ __forceinline__ double operator()(double x, double y) const { return __dadd_rn(x, y); }
+  __device__ __forceinline__ half operator()(half x, half y) const { return x + y; }
 };
 struct OpProd {
   template <class T> __device__ __forceinline__ T operator()(T x, T y) const {
@@ -57,6 +64,7 @@ struct OpProd {
   }
   __device__ __forceinline__ float operator()(float x, float y) const { return __fmul_rn(x, y); }
   __device__ __forceinline__ double operator()(double x, double y) const { return __dmul_rn(x, y); }
+  __device__ __forceinline__ half operator()(half x, half y) const { return x * y; }
 };
 struct OpLand {
   template <class T> __device__ __forceinline__ T operator()(T x, T y) const { return (T)((x != 0) & (y != 0)); }
@@ -83,12 +91,16 @@ template <class F> struct alignas(2 * sizeof(F)) cplx { F re, im; };
 template <class F> __device__ __forceinline__ F fmul_(F a, F b);
 template <> __device__ __forceinline__ float fmul_(float a, float b) { return __fmul_rn(a, b); }
 template <> __device__ __forceinline__ double fmul_(double a, double b) { return __dmul_rn(a, b); }
+template <> __device__ __forceinline__ half fmul_(half a, half b) { return a * b; }
 template <class F> __device__ __forceinline__ F fadd_(F a, F b);
 template <> __device__ __forceinline__ float fadd_(float a, float b) { return __fadd_rn(a, b); }
 template <> __device__ __forceinline__ double fadd_(double a, double b) { return __dadd_rn(a, b); }
+template <> __device__ __forceinline__ half fadd_(half a, half b) { return a + b; }
 template <class F> __device__ __forceinline__ F fsub_(F a, F b);
 template <> __device__ __forceinline__ float fsub_(float a, float b) { return __fsub_rn(a, b); }
 template <> __device__ __forceinline__ double fsub_(double a, double b) { return __dsub_rn(a, b); }
+
+template <> __device__ __forceinline__ half fsub_(half a, half b) { return a - b; }
 
 template <class F> __device__ __forceinline__ F box_(bool inf, F sign_of) {
   return copysign(inf ? (F)1 : (F)0, sign_of);
@@ -135,6 +147,16 @@ __device__ __forceinline__ cplx<F> cmul(cplx<F> p, cplx<F> q) {
   F x = fsub_(ac, bd), y = fadd_(ad, bc);
   if (__builtin_expect(isnan(x) && isnan(y), 0)) cmul_recover<F>(a, b, c, d, ac, bd, ad, bc, x, y);
   return cplx<F>{x, y};
+}
+
+// binary16: the reference has no _Complex type for it and spells the product
+// out (COMPLEX_PROD_FUNC :132-147, p = out, q = in): c0 = q0*p0 - q1*p1,
+// c1 = q0*p1 + q1*p0, each of the six operations rounded to binary16.
+template <>
+__device__ __forceinline__ cplx<half> cmul(cplx<half> p, cplx<half> q) {
+  const half c0 = fsub_(fmul_(q.re, p.re), fmul_(q.im, p.im));
+  const half c1 = fadd_(fmul_(q.re, p.im), fmul_(q.im, p.re));
+  return cplx<half>{c0, c1};
 }
 
 struct OpCsum {

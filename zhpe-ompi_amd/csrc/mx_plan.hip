@@ -577,7 +577,7 @@ using namespace mx;
 extern "C" int mx_allreduce_decision(int n, size_t count, int type) {
   // ompi_coll_tuned_allreduce_intra_dec_fixed (coll_tuned_decision_fixed.c:44-95);
   // every predefined op is commutative.  type < 0 passes -element_size.
-  const size_t es = type < 0 ? (size_t)(-type) : mx_type_size(type);
+  const size_t es = type < 0 ? (size_t)(-type) : type_size(type);
   const size_t block_dsize = es * count;
   if (n <= 1) return MX_ALLREDUCE_RING;
   if (block_dsize < 10000) return MX_ALLREDUCE_RECURSIVE_DOUBLING;
@@ -590,7 +590,7 @@ extern "C" int mx_allreduce_decision(int n, size_t count, int type) {
 
 extern "C" int mx_reduce_scatter_decision(int n, size_t total_count, int type) {
   // ompi_coll_tuned_reduce_scatter_intra_dec_fixed (:466-512)
-  const size_t es = type < 0 ? (size_t)(-type) : mx_type_size(type);
+  const size_t es = type < 0 ? (size_t)(-type) : type_size(type);
   const double a = 0.0012, b = 8.0;
   const size_t small_message_size = 12 * 1024, large_message_size = 256 * 1024;
   const size_t total = total_count * es;
@@ -605,7 +605,7 @@ extern "C" int mx_reduce_scatter_decision(int n, size_t total_count, int type) {
 extern "C" int mx_reduce_decision(int n, size_t count, int type) {
   // ompi_coll_tuned_reduce_intra_dec_fixed (coll_tuned_decision_fixed.c:354-429),
   // commutative ops (every predefined MPI_Op)
-  const size_t es = type < 0 ? (size_t)(-type) : mx_type_size(type);
+  const size_t es = type < 0 ? (size_t)(-type) : type_size(type);
   const double a1 = 0.6016 / 1024.0, b1 = 1.3496, a2 = 0.0410 / 1024.0, b2 = 9.7128;
   const double a3 = 0.0422 / 1024.0, b3 = 1.1614;
   const size_t message_size = es * count;
@@ -620,7 +620,7 @@ extern "C" int mx_reduce_decision(int n, size_t count, int type) {
 
 extern "C" int mx_iallreduce_decision(int n, size_t count, int type, int inplace) {
   // nbc_allreduce_init (nbc_iallreduce.c:113-121), commutative ops
-  const size_t es = type < 0 ? (size_t)(-type) : mx_type_size(type);
+  const size_t es = type < 0 ? (size_t)(-type) : type_size(type);
   if (n < 4 || es * count < 65536 || inplace) return MX_IALLREDUCE_BINOMIAL;
   if (count >= (size_t)pof2_le(n)) return MX_IALLREDUCE_RABENSEIFNER;
   return MX_IALLREDUCE_RING;
@@ -628,7 +628,7 @@ extern "C" int mx_iallreduce_decision(int n, size_t count, int type, int inplace
 
 extern "C" int mx_ireduce_decision(int n, size_t count, int type) {
   // nbc_reduce_init (nbc_ireduce.c:107-116), commutative ops
-  const size_t es = type < 0 ? (size_t)(-type) : mx_type_size(type);
+  const size_t es = type < 0 ? (size_t)(-type) : type_size(type);
   if (n > 2 && count >= (size_t)pof2_le(n)) return MX_IREDUCE_RABENSEIFNER;
   if (n > 4 || es * count < 65536) return MX_IREDUCE_BINOMIAL;
   return MX_IREDUCE_CHAIN;

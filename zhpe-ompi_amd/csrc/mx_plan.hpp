@@ -11,6 +11,7 @@
 
 #include "../../include/mx_kernels.h"
 #include "../../include/mx_coll.h"
+#include "mx_slots.hpp"
 
 namespace mx {
 

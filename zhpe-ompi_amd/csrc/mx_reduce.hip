@@ -474,9 +474,14 @@ static bool is_fortran_slot(int t) {
   }
 }
 
+static bool is_short_float_slot(int t) {
+  return t == MX_TYPE_SHORT_FLOAT || t == MX_TYPE_C_SHORT_FLOAT_COMPLEX;
+}
+
 extern "C" int mx_op_supported(int op, int type, int table_variant) {
   if (op < 0 || op >= MX_OP_COUNT || type < 0 || type >= MX_TYPE_COUNT) return 0;
-  if (table_variant == MX_TABLE_C_ONLY && is_fortran_slot(type)) return 0;
+  if (!(table_variant & MX_TABLE_WITH_FORTRAN) && is_fortran_slot(type)) return 0;
+  if (!(table_variant & MX_TABLE_SHORT_FLOAT) && is_short_float_slot(type)) return 0;
   return lookup(op, type).f2 != nullptr;
 }
 
@@ -502,6 +507,11 @@ extern "C" size_t mx_type_size(int t) {
     default:
       return 0;
   }
+}
+
+extern "C" size_t mx_type_size_ex(int t, int table_variant) {
+  if (is_short_float_slot(t)) return (table_variant & MX_TABLE_SHORT_FLOAT) ? type_size(t) : 0;
+  return mx_type_size(t);
 }
 
 extern "C" int mx_reduce2(int op, int type, const void *in, void *inout, size_t count, void *stream) {

@@ -590,7 +590,7 @@ static bool svc_start(Service &v, svc_launch_fn fn) {
 // command, so no command runs twice and none waits on a held queue.
 int svc_reduce(int op, int type, const void *in, const void *in2, void *inout, size_t count, hipStream_t stream) {
   if (!svc_enabled()) return 0;
-  const size_t es = mx_type_size(type);
+  const size_t es = type_size(type);
   if (!es || count * es > kSvcMaxBytes || (((uintptr_t)in | (uintptr_t)in2 | (uintptr_t)inout) & 15)) return 0;
   SvcVisitor vis;
   const svc_launch_fn fn = dispatch(op, type, vis);

@@ -441,7 +441,7 @@ static int reducible(struct ompi_datatype_t *dtype, struct ompi_op_t *op, size_t
     *slot = mx_ompi_host->dtype_slot(dtype);
     *opi = mx_ompi_host->op_index(op);
     return count > 0 && n <= MX_MAX_RANKS && *slot >= 0 && (mx_ompi_host->op_flags(op) & OMPI_OP_FLAGS_INTRINSIC) &&
-           mx_op_supported(*opi, *slot, MX_TABLE_WITH_FORTRAN);
+           mx_op_supported(*opi, *slot, MX_TABLE_WITH_FORTRAN | MX_TABLE_SHORT_FLOAT);
 }
 
 /* ---- the saved module on host copies (coll/cuda's direction) -----------
@@ -845,7 +845,7 @@ static int mx_coll_reduce_local(const void *inbuf, void *inoutbuf, int count, st
     if ((din || dio) && reducible(dtype, op, (size_t)count, 1, &slot, &opi)) {
         ensure_stream(m);
         if (din && dio) return map_rc(reduce_local_dev(m, opi, slot, inbuf, inoutbuf, (size_t)count));
-        const size_t bytes = (size_t)count * mx_type_size(slot);
+        const size_t bytes = (size_t)count * mx_type_size_ex(slot, MX_TABLE_WITH_FORTRAN | MX_TABLE_SHORT_FLOAT);
         const int kb = mx_ompi_host->mca_int("coll_mi355x_mixed_host_max_kb", 64);
         void *a, *b;
         int rc;

@@ -74,8 +74,22 @@ static struct ompi_datatype_t g_dtypes[] = {
 };
 #define NDT (sizeof g_dtypes / sizeof g_dtypes[0])
 
+/* MXH_SHORT_FLOAT=1 (read by mxh_init, default off) models a reference
+ * configured with a 16-bit float: HAVE_OPAL_SHORT_FLOAT_T and
+ * HAVE_OPAL_SHORT_FLOAT_COMPLEX_T.  It adds the two predefined datatypes of
+ * ompi/mpiext/shortfloat (ids 0x30 / 0x31, ompi_datatype_internal.h:108-109;
+ * slots 14 / 26, op.c:228-229) and the six (op, type) base functions below. */
+static int g_short_float;
+static struct ompi_datatype_t g_sf_dtypes[] = {
+    DT("MPIX_SHORT_FLOAT", 0x30, 14, 2), DT("MPIX_C_FLOAT16", 0x30, 14, 2),
+    DT("MPIX_C_SHORT_FLOAT_COMPLEX", 0x31, 26, 4),
+};
+#define NSFDT (sizeof g_sf_dtypes / sizeof g_sf_dtypes[0])
+
 void *mxh_dtype(const char *name)
 {
+    for (size_t i = 0; g_short_float && i < NSFDT; i++)
+        if (!strcmp(g_sf_dtypes[i].name, name)) return &g_sf_dtypes[i];
     for (size_t i = 0; i < NDT; i++)
         if (!strcmp(g_dtypes[i].name, name)) return &g_dtypes[i];
     return NULL;
@@ -159,6 +173,135 @@ static void base_3buff(void *in1, void *in2, void *out, int *count, struct ompi_
     g_base(((base_op_module_t *)m)->op, (*dt)->slot, in2, out, (size_t)*count, 1);
 }
 
+/* ---- binary16 base functions (MXH_SHORT_FLOAT) -----------------------------
+ * The reference's FUNC_FUNC / OP_FUNC / COMPLEX_*_FUNC on opal_short_float_t
+ * (op_base_functions.c:184-187 ... 403-406, 3-buffer :812-815 ... 1031-1034).
+ * This host's compiler has no _Float16: every operation is an exact
+ * half -> float conversion, one float operation and one round-to-nearest-even
+ * float -> half conversion.  The float result of a sum or product of two
+ * binary16 values rounds to binary16 as the exact result does (24 >= 2 * 11
+ * + 2 significand bits), so each operation is one correctly rounded binary16
+ * operation. */
+float mxh_half_to_float(uint16_t h)
+{
+    const uint32_t sign = (uint32_t)(h & 0x8000) << 16;
+    uint32_t e = (h >> 10) & 0x1f, m = h & 0x3ff, x;
+    float f;
+    if (e == 0x1f) {
+        x = sign | 0x7f800000u | (m << 13);            /* infinity, NaN (payload kept) */
+    } else if (e) {
+        x = sign | ((e + 112) << 23) | (m << 13);
+    } else if (m) {                                    /* subnormal: normalise */
+        e = 113;
+        while (!(m & 0x400)) { m <<= 1; e--; }
+        x = sign | (e << 23) | ((m & 0x3ff) << 13);
+    } else {
+        x = sign;
+    }
+    memcpy(&f, &x, 4);
+    return f;
+}
+
+uint16_t mxh_float_to_half(float f)
+{
+    uint32_t x, e, m, h, rem, half;
+    int shift;
+    memcpy(&x, &f, 4);
+    const uint16_t sign = (uint16_t)((x >> 16) & 0x8000);
+    x &= 0x7fffffffu;
+    e = x >> 23;
+    m = x & 0x7fffffu;
+    if (e == 0xff) {                                   /* infinity; NaN stays NaN */
+        h = 0x7c00 | (m >> 13);
+        if (m && !(h & 0x3ff)) h |= 0x200;
+        return (uint16_t)(sign | h);
+    }
+    if (e >= 143) return (uint16_t)(sign | 0x7c00);    /* >= 2^16: overflow */
+    if (e < 101) return sign;                          /* < 2^-26: rounds to zero */
+    if (e >= 113) {                                    /* normal binary16 */
+        h = ((e - 112) << 10) | (m >> 13);
+        shift = 13;
+    } else {                                           /* subnormal binary16 */
+        m |= 0x800000u;
+        shift = (int)(126 - e);                        /* 14 .. 25 */
+        h = m >> shift;
+    }
+    rem = m & ((1u << shift) - 1);
+    half = 1u << (shift - 1);
+    if (rem > half || (rem == half && (h & 1))) h++;   /* a carry walks into the exponent, up to infinity */
+    return (uint16_t)(sign | h);
+}
+
+static uint16_t sf_add(uint16_t a, uint16_t b)
+{
+    return mxh_float_to_half(mxh_half_to_float(a) + mxh_half_to_float(b));
+}
+static uint16_t sf_sub(uint16_t a, uint16_t b)
+{
+    return mxh_float_to_half(mxh_half_to_float(a) - mxh_half_to_float(b));
+}
+static uint16_t sf_mul(uint16_t a, uint16_t b)
+{
+    return mxh_float_to_half(mxh_half_to_float(a) * mxh_half_to_float(b));
+}
+
+/* one element: x = the reference's first operand (2-buffer: out, 3-buffer:
+ * in1), y the second; x and r may be the same object */
+static void sf_elem(int op, int cplx, const uint16_t *x, const uint16_t *y, uint16_t *r)
+{
+    if (!cplx) {
+        switch (op) {
+        case 1: r[0] = mxh_half_to_float(x[0]) > mxh_half_to_float(y[0]) ? x[0] : y[0]; break;   /* :154 */
+        case 2: r[0] = mxh_half_to_float(x[0]) < mxh_half_to_float(y[0]) ? x[0] : y[0]; break;
+        case 3: r[0] = sf_add(x[0], y[0]); break;
+        default: r[0] = sf_mul(x[0], y[0]); break;
+        }
+    } else if (op == 3) {                              /* COMPLEX_SUM_FUNC :112-124 */
+        r[0] = sf_add(x[0], y[0]);
+        r[1] = sf_add(x[1], y[1]);
+    } else {                                           /* COMPLEX_PROD_FUNC :132-147, a = y, b = x */
+        const uint16_t c0 = sf_sub(sf_mul(y[0], x[0]), sf_mul(y[1], x[1]));
+        const uint16_t c1 = sf_add(sf_mul(y[0], x[1]), sf_mul(y[1], x[0]));
+        r[0] = c0;
+        r[1] = c1;
+    }
+}
+
+static int sf_has(int op, int t)
+{
+    return (t == 14 && op >= 1 && op <= 4) || (t == 26 && (op == 3 || op == 4));
+}
+
+/* test entry: inout = inout OP in (in2 == NULL) or inout = in OP in2 */
+int mxh_short_float_reduce(int op, int type, const void *in, const void *in2, void *inout, size_t n)
+{
+    const int w = type == 26 ? 2 : 1;
+    const uint16_t *a = in, *b = in2;
+    uint16_t *o = inout;
+    if (!sf_has(op, type)) return -1;
+    for (size_t i = 0; i < n; i++) {
+        if (b) sf_elem(op, w == 2, a + i * w, b + i * w, o + i * w);
+        else sf_elem(op, w == 2, o + i * w, a + i * w, o + i * w);
+    }
+    return 0;
+}
+
+static void sf_2buff(void *in, void *inout, int *count, struct ompi_datatype_t **dt, ompi_op_base_module_t *m)
+{
+    mxh_short_float_reduce(((base_op_module_t *)m)->op, (*dt)->slot, in, NULL, inout, (size_t)*count);
+}
+static void sf_3buff(void *in1, void *in2, void *out, int *count, struct ompi_datatype_t **dt,
+                     ompi_op_base_module_t *m)
+{
+    mxh_short_float_reduce(((base_op_module_t *)m)->op, (*dt)->slot, in1, in2, out, (size_t)*count);
+}
+
+/* the table's non-NULL pattern: the injected one, plus the binary16 slots */
+static int base_has(int op, int t)
+{
+    return g_pattern(op, t, 1) != 0 || (g_short_float && sf_has(op, t));
+}
+
 void *mxh_op(const char *name)
 {
     for (int i = 0; i < OMPI_OP_BASE_FORTRAN_OP_MAX; i++)
@@ -172,6 +315,14 @@ int mxh_op_slot_owner(void *opv, int t, int three)
     ompi_op_base_module_t *m = three ? op->o_3buff_intrinsic.modules[t] : op->intrinsic.modules[t];
     if (!m) return -1;
     return (m == &g_base_mod[op->o_f_to_c_index].super) ? 0 : 1;
+}
+
+/* 1 when slot t of the op's 2- or 3-buffer table holds a function */
+int mxh_op_slot_set(void *opv, int t, int three)
+{
+    struct ompi_op_t *op = opv;
+    if (t < 0 || t >= OMPI_OP_BASE_TYPE_MAX) return 0;
+    return (three ? (void *)op->o_3buff_intrinsic.fns[t] : (void *)op->intrinsic.fns[t]) != NULL;
 }
 
 /* ---- MCA variables --------------------------------------------------------- */
@@ -1085,10 +1236,11 @@ static int op_select(struct ompi_op_t *op)
     bm->super.super.obj_reference_count = 1;
     bm->op = op->o_f_to_c_index;
     for (int t = 0; t < OMPI_OP_BASE_TYPE_MAX; t++) {
-        const int has = g_pattern(op->o_f_to_c_index, t, 1);
-        op->intrinsic.fns[t] = has ? base_2buff : NULL;
+        const int has = base_has(op->o_f_to_c_index, t);
+        const int sf = g_short_float && sf_has(op->o_f_to_c_index, t);
+        op->intrinsic.fns[t] = sf ? sf_2buff : has ? base_2buff : NULL;
         op->intrinsic.modules[t] = &bm->super;
-        op->o_3buff_intrinsic.fns[t] = has ? base_3buff : NULL;
+        op->o_3buff_intrinsic.fns[t] = sf ? sf_3buff : has ? base_3buff : NULL;
         op->o_3buff_intrinsic.modules[t] = &bm->super;
         obj_retain(&bm->super.super);
         obj_retain(&bm->super.super);
@@ -1116,7 +1268,7 @@ static int op_select(struct ompi_op_t *op)
     obj_release(&m->super);
     /* NULL-pattern sanity check (:185-201) */
     for (int t = 0; t < OMPI_OP_BASE_TYPE_MAX; t++)
-        if ((g_pattern(op->o_f_to_c_index, t, 1) != 0) != (op->intrinsic.fns[t] != NULL)) return OMPI_ERR_NOT_FOUND;
+        if (base_has(op->o_f_to_c_index, t) != (op->intrinsic.fns[t] != NULL)) return OMPI_ERR_NOT_FOUND;
     return 0;
 }
 
@@ -1258,6 +1410,10 @@ int mxh_init(const char *component_lib, mxh_reducer_t base, mxh_pattern_t patter
 {
     g_base = base;
     g_pattern = pattern;
+    {
+        const char *sf = getenv("MXH_SHORT_FLOAT");
+        g_short_float = sf && *sf && *sf != '0';
+    }
     g_host = (mx_ompi_host_t){comm_rank, comm_size, dtype_slot, dtype_size, dtype_contiguous, op_index, op_flags,
                               op_fns, op_3fns, comm_coll_fn, obj_retain, obj_release, mca_int, NULL};
     g_host.byte_dtype = mxh_dtype("MPI_BYTE");

@@ -62,11 +62,23 @@ int mxh_set_mca(const char *name, int value);
 int mxh_set_mca_str(const char *name, const char *value);
 
 void *mxh_dtype(const char *mpi_name);   /* MPI_FLOAT, MPI_2INT, ...; NULL if unknown */
+/* MXH_SHORT_FLOAT=1 in the environment of mxh_init (default off) models a
+ * reference configured with a 16-bit float (HAVE_OPAL_SHORT_FLOAT_T +
+ * HAVE_OPAL_SHORT_FLOAT_COMPLEX_T): MPIX_SHORT_FLOAT, MPIX_C_FLOAT16 and
+ * MPIX_C_SHORT_FLOAT_COMPLEX exist, and their six (op, type) slots hold base
+ * functions computed in plain C (one correctly rounded binary16 operation
+ * each).  The conversions and the functions themselves, for the tests
+ * (in2 == NULL: inout = inout OP in; else inout = in OP in2): */
+float mxh_half_to_float(uint16_t h);
+uint16_t mxh_float_to_half(float f);
+int mxh_short_float_reduce(int op, int type, const void *in, const void *in2, void *inout, size_t n);
 void *mxh_dtype_contiguous(int count, void *oldtype);  /* MPI_Type_contiguous */
 void *mxh_dtype_vector(int count, int blocklen, int stride, void *oldtype);  /* MPI_Type_vector */
 void *mxh_op(const char *mpi_name);      /* MPI_SUM, MPI_MAXLOC, ... */
 /* which module owns slot t of op: 0 base, 1 mi355x */
 int mxh_op_slot_owner(void *op, int type, int three_buffer);
+/* 1 when slot t of the op's table is non-NULL */
+int mxh_op_slot_set(void *op, int type, int three_buffer);
 
 void *mxh_comm_create(int rank, int size, mxh_allgather_t ag, void *ctx);
 void *mxh_comm_self(void);

@@ -50,6 +50,9 @@
 static int h_rank(struct ompi_communicator_t *c) { return ompi_comm_rank(c); }
 static int h_size(struct ompi_communicator_t *c) { return ompi_comm_size(c); }
 
+/* MPIX_SHORT_FLOAT / MPIX_C_SHORT_FLOAT_COMPLEX (ids 0x30 / 0x31,
+ * ompi_datatype_internal.h:108-109) come through the same map as
+ * OMPI_OP_BASE_TYPE_SHORT_FLOAT / _C_SHORT_FLOAT_COMPLEX (op.c:228-229) */
 static int h_slot(struct ompi_datatype_t *dt)
 {
     if (!ompi_datatype_is_predefined(dt)) {

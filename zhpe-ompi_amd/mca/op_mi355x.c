@@ -36,6 +36,10 @@
 #ifndef MX_OMPI_WITH_FORTRAN
 #define MX_OMPI_WITH_FORTRAN 1   /* table variant of the host Open MPI build */
 #endif
+/* every slot the library has a kernel for: the binary16 slots are non-NULL
+ * on the op only in a host built with a 16-bit float, and a NULL slot is
+ * left alone below */
+#define MX_OMPI_TABLE (MX_OMPI_WITH_FORTRAN | MX_TABLE_SHORT_FLOAT)
 
 #ifndef MX_OMPI_REAL
 /* one library holds both components here; in an Open MPI tree each
@@ -210,7 +214,7 @@ static void mx_op_2buff(void *in, void *inout, int *count, struct ompi_datatype_
         run2(m, slot, in, inout, (size_t)*count, s);
         return;
     }
-    const size_t bytes = (size_t)*count * mx_type_size(slot);
+    const size_t bytes = (size_t)*count * mx_type_size_ex(slot, MX_OMPI_TABLE);
     if (dio || bytes > mixed_host_max()) {   /* compute on the device */
         void *din_p = stage(in, din, 1, bytes, 0, 1, s);
         void *dio_p = stage(inout, dio, 1, bytes, 1, 1, s);
@@ -246,7 +250,7 @@ static void mx_op_3buff(void *in1, void *in2, void *out, int *count, struct ompi
         run3(m, slot, in1, in2, out, (size_t)*count, s);
         return;
     }
-    const size_t bytes = (size_t)*count * mx_type_size(slot);
+    const size_t bytes = (size_t)*count * mx_type_size_ex(slot, MX_OMPI_TABLE);
     if (dout || bytes > mixed_host_max()) {   /* compute on the device */
         void *a = stage(in1, d1, 1, bytes, 0, 1, s);
         void *b = stage(in2, d2, 1, bytes, 1, 1, s);
@@ -290,7 +294,7 @@ static ompi_op_base_module_t *mx_op_component_op_query(struct ompi_op_t *op, int
         /* only slots that have a kernel AND are non-NULL on the op: the
          * framework requires the NULL pattern to stay identical
          * (op_base_op_select.c:185-201) */
-        if (!mx_op_supported(idx, t, MX_OMPI_WITH_FORTRAN)) continue;
+        if (!mx_op_supported(idx, t, MX_OMPI_TABLE)) continue;
         if (cur->fns[t]) {
             m->super.opm_fns[t] = mx_op_2buff;
             m->fallback[t] = cur->fns[t];

@@ -41,6 +41,7 @@ TYPE = {name: i for i, name in enumerate(TYPES)}
 
 TABLE_C_ONLY = 0
 TABLE_WITH_FORTRAN = 1
+TABLE_SHORT_FLOAT = 2              # flag, or-ed onto either variant (MX_TABLE_SHORT_FLOAT)
 
 # MPI predefined datatype -> op type slot (restates ompi/op/op.c:131-229 with
 # the C aliases of ompi/datatype/ompi_datatype_internal.h:130-200 for LP64).
@@ -66,6 +67,11 @@ MPI_DTYPE_SLOT = {
     "MPI_C_COMPLEX": "C_FLOAT_COMPLEX", "MPI_C_FLOAT_COMPLEX": "C_FLOAT_COMPLEX",
     "MPI_C_DOUBLE_COMPLEX": "C_DOUBLE_COMPLEX",
     "MPI_C_LONG_DOUBLE_COMPLEX": "C_LONG_DOUBLE_COMPLEX", "MPI_COUNT": "INT64_T",
+}
+# ompi/mpiext/shortfloat (op.c:228-229): present where the host has a 16-bit float
+MPIX_DTYPE_SLOT = {
+    "MPIX_SHORT_FLOAT": "SHORT_FLOAT", "MPIX_C_FLOAT16": "SHORT_FLOAT",
+    "MPIX_C_SHORT_FLOAT_COMPLEX": "C_SHORT_FLOAT_COMPLEX",
 }
 
 ERRORS = {0: "MX_SUCCESS", -1: "MX_ERR_ARG", -2: "MX_ERR_UNSUPPORTED", -3: "MX_ERR_HIP",
@@ -109,6 +115,8 @@ def lib() -> ctypes.CDLL:
         L.mx_version.restype = ctypes.c_char_p
         L.mx_type_size.restype = sz
         L.mx_type_size.argtypes = [i]
+        L.mx_type_size_ex.restype = sz
+        L.mx_type_size_ex.argtypes = [i, i]
         L.mx_op_supported.argtypes = [i, i, i]
         L.mx_reduce2.argtypes = [i, i, vp, vp, sz, vp]
         L.mx_reduce2_sync.argtypes = [i, i, vp, vp, sz, vp]
@@ -134,6 +142,8 @@ def check(rc: int, what: str = "mx call") -> int:
 def _slot(v) -> int:
     """Type slot from a slot name ("FLOAT"), an MPI datatype name ("MPI_FLOAT") or an int."""
     if isinstance(v, str):
+        if v.startswith("MPIX_"):
+            return TYPE[MPIX_DTYPE_SLOT[v]]
         return TYPE[MPI_DTYPE_SLOT[v]] if v.startswith("MPI_") else TYPE[v]
     return int(v)
 
@@ -149,7 +159,14 @@ def type_size(t) -> int:
     return int(lib().mx_type_size(_slot(t)))
 
 
+def type_size_ex(t, table=TABLE_WITH_FORTRAN | TABLE_SHORT_FLOAT) -> int:
+    """Element size under a table variant: with TABLE_SHORT_FLOAT the
+    binary16 slots are 2 and 4 bytes (type_size keeps them at 0)."""
+    return int(lib().mx_type_size_ex(_slot(t), table))
+
+
 def op_supported(op, t, table=TABLE_WITH_FORTRAN) -> bool:
+    """`table`: TABLE_C_ONLY or TABLE_WITH_FORTRAN, optionally | TABLE_SHORT_FLOAT."""
     return bool(lib().mx_op_supported(_op(op), _slot(t), table))
 
 
