@@ -85,26 +85,35 @@ def _env(env):
     return e
 
 
+MAX_CHILDREN = 8   # at a time: with this process, well under 16 processes holding the GPU open
+
+
 def _run_all(cases):
-    """Every (env, types) case in its own child process, all at once (the
-    switches are read once per process; a child's run is mostly its own
-    start-up, so they overlap it): each must exit 0."""
-    procs = [(env, subprocess.Popen([sys.executable, "-c", CHILD, ROOT, types], stdout=subprocess.PIPE,
-                                    stderr=subprocess.PIPE, text=True, env=_env(env))) for env, types in cases]
+    """Every (env, types) case in its own child process, MAX_CHILDREN at a
+    time (the switches are read once per process; a child's run is mostly
+    its own start-up, so they overlap it): each must exit 0."""
     failed = []
-    for env, p in procs:
-        try:
-            out, err = p.communicate(timeout=240)
-        except subprocess.TimeoutExpired:
-            p.kill()
-            out, err = p.communicate()
-        if p.returncode != 0:
-            failed.append((env, p.returncode, out[-2000:], err[-3000:]))
+    for i in range(0, len(cases), MAX_CHILDREN):
+        procs = [(env, subprocess.Popen([sys.executable, "-c", CHILD, ROOT, types], stdout=subprocess.PIPE,
+                                        stderr=subprocess.PIPE, text=True, env=_env(env)))
+                 for env, types in cases[i:i + MAX_CHILDREN]]
+        for env, p in procs:
+            try:
+                out, err = p.communicate(timeout=240)
+            except subprocess.TimeoutExpired:
+                p.kill()
+                out, err = p.communicate()
+            if p.returncode != 0:
+                failed.append((env, p.returncode, out[-2000:], err[-3000:]))
+        if failed:   # start nothing more after a failure
+            break
     assert not failed, failed
 
 
-BMAP_SWITCHES = ["MX_CONV_BMAP_SPAN=12288", "MX_CONV_BMAP_SPAN=24576", "MX_CONV_BMAP_UNROLL=0", "MX_CONV_BMAP_QUAD=0",
-                 "MX_CONV_BMAP_WORD=1", "MX_CONV_BMAP_NT=0", "MX_CONV_BMAP_DW=0", "MX_CONV_BMAP_CW=0",
+BMAP_SWITCHES = ["MX_CONV_BMAP_SPAN=12288", "MX_CONV_BMAP_SPAN=24576", "MX_CONV_BMAP_SPAN=49152",
+                 "MX_CONV_BMAP_UNROLL=0", "MX_CONV_BMAP_QUAD=0",
+                 "MX_CONV_BMAP_WORD=1", "MX_CONV_BMAP_NT=0", "MX_CONV_BMAP_DW=0", "MX_CONV_BMAP_DW=0 MX_CONV_BMAP_NT=0",
+                 "MX_CONV_BMAP_CW=0",
                  "MX_NT_MIN_BYTES=0 MX_CONV_UNPACK_NTLD=1", "MX_CONV_BMAP_INST=0",
                  # the piece unpack forms (by default measured per datatype: staged or one piece per lane)
                  "MX_CONV_UNPACK_DIRECT=0", "MX_CONV_UNPACK_DIRECT=1", "MX_CONV_UNPACK_DIRECT=0 MX_CONV_UNPACK_U32=0",

@@ -377,17 +377,18 @@ __global__ void __launch_bounds__(kCB) k_pack_vec_span(const char *ubase, char *
 // One mapping (three multiply-shift divisions) per lane instead of one per
 // byte; HBM sees only wide accesses.
 // ---------------------------------------------------------------------------
-// TP = stream bytes per tile (TP / kCB per lane); a PACK tile may stage up
-// to 3 * TP user bytes.  Each piece's user address is advanced in place
-// (next block: + stride1; next outer block / run / instance: from the
-// instance base) instead of being recomputed with 64-bit multiplies.
-template <int TP> struct TileGeom {
-  static constexpr int kChunk = TP / kCB;
-  static constexpr int kSpanCap = 3 * TP;
-  static constexpr size_t lds(bool pack, size_t run_bytes) {
-    return TP + 16 + (pack ? kSpanCap + 32 : 0) + run_bytes;
-  }
-};
+// kTP = stream bytes per tile (kChunk per lane; 2048 and 4096 were measured
+// with a switch since removed, profiles/r01/convertor_tile_tp_ab.txt); a
+// PACK tile may stage up to kTileSpanCap user bytes.  Each piece's user
+// address is advanced in place (next block: + stride1; next outer block /
+// run / instance: from the instance base) instead of being recomputed with
+// 64-bit multiplies.
+constexpr int kTP = 8192;
+constexpr int kChunk = kTP / kCB;
+constexpr int kTileSpanCap = 3 * kTP;
+constexpr size_t tile_lds(bool pack, size_t run_bytes) {
+  return kTP + 16 + (pack ? kTileSpanCap + 32 : 0) + run_bytes;
+}
 
 __device__ __forceinline__ uint32_t lds_word(const char *s) {  // 4 bytes at any alignment
   const uintptr_t u = (uintptr_t)s;
@@ -436,10 +437,9 @@ __device__ __forceinline__ void tile_move(char *lds, char *glob, uint64_t nbytes
 // One lane's kChunk-byte stretch of tile [r0, r1): PACK copies pieces from
 // the staged user span (LDS, origin `lo`) into the packed tile (LDS),
 // UNPACK stores pieces from the packed tile straight to user memory.
-template <bool PACK, int TP>
+template <bool PACK>
 __device__ __forceinline__ void walk_chunk(const ConvArgs &a, const DRun *runs, char *pk, const char *span,
                                            uintptr_t lo, uint64_t r0, uint64_t r1) {
-  constexpr int kChunk = TileGeom<TP>::kChunk;
   const uint64_t c0 = r0 + (uint64_t)threadIdx.x * kChunk;
   const uint64_t c1 = c0 + kChunk < r1 ? c0 + kChunk : r1;
   if (c0 < c1) {
@@ -479,9 +479,9 @@ __device__ __forceinline__ void walk_chunk(const ConvArgs &a, const DRun *runs, 
   }
 }
 
-template <bool PACK, int TP>
+template <bool PACK>
 __global__ void __launch_bounds__(kCB) k_convert_tile(ConvArgs a, int nruns_lds, int wordpar) {
-  constexpr int kTP = TP, kSpanCap = TileGeom<TP>::kSpanCap;
+  constexpr int kSpanCap = kTileSpanCap;
   extern __shared__ __align__(16) char smem[];
   char *pk = smem;                                   // kTP (+16 slack)
   char *span = smem + kTP + 16;                      // kSpanCap (+32 slack), PACK only
@@ -539,7 +539,7 @@ __global__ void __launch_bounds__(kCB) k_convert_tile(ConvArgs a, int nruns_lds,
     }
     return;
   }
-  walk_chunk<PACK, TP>(a, runs, pk, span, lo, r0, r1);
+  walk_chunk<PACK>(a, runs, pk, span, lo, r0, r1);
   if (PACK) {
     __syncthreads();
     tile_move<false>(pk, a.packed + r0, r1 - r0, vec);
@@ -553,25 +553,27 @@ __global__ void __launch_bounds__(kCB) k_convert_tile(ConvArgs a, int nruns_lds,
 // kernel above idles the memory pipe during every LDS phase (SQ counters on
 // the struct type: ~730 VALU instructions per 22.6k-cycle wave, i.e. waves
 // mostly wait on the span load).
-// Geometry (TP stream bytes per tile, SPAN bytes of user span staged): each
-// lane owns TP / kCB consecutive stream bytes, so at every step of the walk
-// the 64 lanes of a wave write the packed tile at a stride of TP / kCB
-// bytes.  With 32-byte stretches (TP 8192) lane starts fall on only 8 of
-// the 64 LDS banks (8-way conflicts, SQ_LDS_BANK_CONFLICT 2.7 cycles per LDS
-// instruction on the struct type); 36-byte stretches (TP 9216, 9 dwords,
-// coprime to 64) start every lane of a wave on its own bank.  A smaller span
-// cap (16 KiB: the struct type reads 48/29 x TP) lets 6 instead of 4
-// workgroups share a CU.
-template <int TP, int SPAN>
-struct PipeGeom {
-  static constexpr int kSpanCap = SPAN;
-  static constexpr int kPre = SPAN / 16 / kCB;   // uint4 per lane for a full span
-  static constexpr size_t lds(size_t run_bytes) { return TP + 16 + SPAN + 32 + run_bytes; }
-};
+// Geometry (kTP stream bytes per tile, kPipeSpan bytes of user span staged,
+// kPipeWgs workgroups per CU): each lane owns kChunk consecutive stream
+// bytes, so at every step of the walk the 64 lanes of a wave write the
+// packed tile at a stride of kChunk bytes.  With 32-byte stretches (8192)
+// lane starts fall on only 8 of the 64 LDS banks (8-way conflicts,
+// SQ_LDS_BANK_CONFLICT 2.7 cycles per LDS instruction on the struct type);
+// 36-byte stretches (9216, 9 dwords, coprime to 64) start every lane of a
+// wave on its own bank, and a smaller span cap (16 KiB: the struct type
+// reads 48/29 x the tile) lets 6 instead of 4 workgroups share a CU.
+// 8192 x 24 KiB was fastest on every type measured against 9216 x 16 KiB,
+// 9216 x 28 KiB and 8192 x 16 KiB (with a switch since removed,
+// profiles/r02/convertor_r2.txt): the bank-conflict-free stretches lose
+// more to the tile / occupancy change than the conflicts cost (20k of ~4M
+// cycles per wave).
+constexpr int kPipeSpan = 24576;
+constexpr int kPipeWgs = 4;
+constexpr int kPipePre = kPipeSpan / 16 / kCB;   // uint4 per lane for a full span
+constexpr size_t pipe_lds(size_t run_bytes) { return kTP + 16 + kPipeSpan + 32 + run_bytes; }
 
-template <int TP, int SPAN>
 __global__ void __launch_bounds__(kCB) k_pack_tile_pipe(ConvArgs a, int nruns_lds, uint64_t ntiles) {
-  constexpr int kTP = TP, kSpanCap = SPAN, kPre = PipeGeom<TP, SPAN>::kPre;
+  constexpr int kSpanCap = kPipeSpan, kPre = kPipePre;
   static_assert(kSpanCap % (16 * kCB) == 0, "span staging is whole vectors per lane");
   static_assert(kTP % (16 * 4) == 0 && kTP / kCB >= 16, "tiles are whole 16-byte vectors");
   extern __shared__ __align__(16) char smem[];
@@ -622,7 +624,7 @@ __global__ void __launch_bounds__(kCB) k_pack_tile_pipe(ConvArgs a, int nruns_ld
     }
     const uint64_t r0 = t * kTP, r1 = r0 + kTP < a.len ? r0 + kTP : a.len;
     if (s_ok[cur]) {
-      walk_chunk<true, TP>(a, runs, pk, span, s_lo[cur], r0, r1);
+      walk_chunk<true>(a, runs, pk, span, s_lo[cur], r0, r1);
       __syncthreads();
       tile_move<false>(pk, a.packed + r0, r1 - r0, a.pk_vec);
     } else {                                         // span too wide for LDS: per-granule gather
@@ -681,7 +683,6 @@ struct BmapArgs {
   uint64_t ntiles;
   uint32_t adv_b;          // kCB * 4 stream bytes = adv_io / ext instances + adv_b bytes
   int64_t adv_io;
-  uint64_t lo_mask;        // a tile's staged span starts at lo & ~lo_mask (15, or 127: whole lines)
   uint32_t qsh;            // 2: the map is staged as quads (entry b at [4b], its dword's bytes at [4b..4b+3])
   uint32_t cw;             // try one LDS dword read per packed dword (word-piece layouts)
   uint32_t unroll;         // kBmapU dwords per lane per step in the DW gather
@@ -690,11 +691,11 @@ struct BmapArgs {
 constexpr int kBmapU = 4;
 
 // M = uint16_t when the instance's user span is below 64 KiB, else uint32_t.
-// PIPE (round 3): persistent workgroups keep the NEXT tile's user span in
-// flight in registers (SPAN / 16 / kCB uint4 per lane) while the lanes
+// Pipelined (round 3): persistent workgroups keep the NEXT tile's user span
+// in flight in registers (SPAN / 16 / kCB uint4 per lane) while the lanes
 // gather the current tile out of LDS -- without it every tile's span load
 // and gather run back to back inside the workgroup.
-template <int SPAN, class M, bool DW, bool PIPE, bool NT>
+template <int SPAN, class M, bool DW, bool NT>
 // waves per SIMD the LDS allows (workgroups per CU: 6 at a 24 KiB span), so
 // the register budget never lowers the occupancy below it
 __global__ void __launch_bounds__(kCB, SPAN >= 49152 ? 3 : SPAN >= 24576 ? 6 : 7) k_pack_bmap(BmapArgs a) {
@@ -748,7 +749,7 @@ __global__ void __launch_bounds__(kCB, SPAN >= 49152 ? 3 : SPAN >= 24576 ? 6 : 7
       lo = ubase + ent(sa - ia * a.S);
       hi = ubase + (int64_t)(ib - ia) * a.ext + ent(s1 - 1 - ib * a.S) + 1;
     }
-    s_lo[slot] = lo & ~(uintptr_t)a.lo_mask;
+    s_lo[slot] = lo & ~(uintptr_t)(kBmapAlign - 1);           // whole lines: a wave's 1 KiB loads cover them
     s_hi[slot] = (hi + 15) & ~(uintptr_t)15;
   };
   auto gather = [&](uint64_t t, uintptr_t lo) {
@@ -906,22 +907,6 @@ __global__ void __launch_bounds__(kCB, SPAN >= 49152 ? 3 : SPAN >= 24576 ? 6 : 7
       }
     }
   };
-  if (!PIPE) {
-    for (uint64_t t = blockIdx.x; t < a.ntiles; t += gridDim.x) {
-      __syncthreads();                                        // map staged; previous tile done with span
-      if (threadIdx.x == 0) bounds(t, 0);
-      __syncthreads();
-      {
-        const char *g = reinterpret_cast<const char *>(s_lo[0]);
-        uint4 *d = reinterpret_cast<uint4 *>(span);
-        const uint32_t nv = (uint32_t)((s_hi[0] - s_lo[0]) / 16);
-        for (uint32_t i = threadIdx.x; i < nv; i += kCB) d[i] = gld16p<NT>(g + 16 * (size_t)i);
-      }
-      __syncthreads();
-      gather(t, s_lo[0]);
-    }
-    return;
-  }
   uint64_t t = blockIdx.x;
   if (t >= a.ntiles) return;
   __syncthreads();                                            // map staged
@@ -989,14 +974,13 @@ __device__ __forceinline__ void piece_store(char *u, int lg, uint32_t v0, uint32
   }
 }
 
-// PIPE: the packed range of the workgroup's next tile is loaded into
-// registers (kPieceStage / 16 / kCB 16-byte vectors per lane) while the
-// lanes store the current tile from LDS.  Measured slower (round 4,
-// interleaved A/B at 1 GiB, profiles/r04/unpack_pipe_ab.txt: BLACS 1540 ->
-// 1577 us, struct 949 -> 1071 us): the unpack is bound by its partial-line
-// stores, and loads kept in flight beside them only compete (64 more VGPRs
-// per lane, fewer waves); so it is off (MX_CONV_UNPACK_PIPE=1 turns it on).
-template <bool PIPE, bool TL>
+// One tile at a time, no prefetch: loading the workgroup's next tile into
+// registers while the lanes store the current one measured slower (round 4,
+// with a switch since removed, interleaved A/B at 1 GiB,
+// profiles/r04/unpack_pipe_ab.txt: BLACS 1540 -> 1577 us, struct 949 ->
+// 1071 us): the unpack is bound by its partial-line stores, and loads kept
+// in flight beside them only compete (64 more VGPRs per lane, fewer waves).
+template <bool TL>
 __global__ void __launch_bounds__(kCB) k_unpack_piece(PieceArgs a) {
   extern __shared__ __align__(16) char smem[];
   char *stage = smem;                                        // kPieceStage + 48
@@ -1099,58 +1083,21 @@ __global__ void __launch_bounds__(kCB) k_unpack_piece(PieceArgs a) {
       if (j >= a.npi) { j -= a.npi; inst++; }
     }
   };
-  if constexpr (!PIPE) {
-    for (uint64_t t = blockIdx.x; t < a.ntiles; t += gridDim.x) {
-      uintptr_t lo, hi;
-      range(t, lo, hi);
-      __syncthreads();                                        // previous tile consumed
-      {
-        const uint4 *g = reinterpret_cast<const uint4 *>(lo);
-        uint4 *d = reinterpret_cast<uint4 *>(stage);
-        const uint32_t nv = (uint32_t)((hi - lo) / 16);
-        if (a.ntld)
-          for (uint32_t i = threadIdx.x; i < nv; i += kCB) d[i] = gld16p<true>(reinterpret_cast<const char *>(g + i));
-        else
-          for (uint32_t i = threadIdx.x; i < nv; i += kCB) d[i] = gld16(reinterpret_cast<const char *>(g + i));
-      }
-      __syncthreads();
-      store_tile(t, lo);
-    }
-  } else {
-    constexpr int kPre = kPieceStage / 16 / kCB;
-    uint64_t t = blockIdx.x;
-    if (t >= a.ntiles) return;
+  for (uint64_t t = blockIdx.x; t < a.ntiles; t += gridDim.x) {
     uintptr_t lo, hi;
     range(t, lo, hi);
+    __syncthreads();                                        // previous tile consumed
     {
       const uint4 *g = reinterpret_cast<const uint4 *>(lo);
       uint4 *d = reinterpret_cast<uint4 *>(stage);
       const uint32_t nv = (uint32_t)((hi - lo) / 16);
-      for (uint32_t i = threadIdx.x; i < nv; i += kCB) d[i] = g[i];
+      if (a.ntld)
+        for (uint32_t i = threadIdx.x; i < nv; i += kCB) d[i] = gld16p<true>(reinterpret_cast<const char *>(g + i));
+      else
+        for (uint32_t i = threadIdx.x; i < nv; i += kCB) d[i] = gld16(reinterpret_cast<const char *>(g + i));
     }
-    for (;;) {
-      const uint64_t tn = t + gridDim.x;
-      const bool has_next = tn < a.ntiles;
-      uintptr_t nlo = 0, nhi = 0;
-      if (has_next) range(tn, nlo, nhi);
-      uint4 pre[kPre];
-      const uint32_t nvn = (uint32_t)((nhi - nlo) / 16);
-#pragma unroll
-      for (int k = 0; k < kPre; k++)
-        if (threadIdx.x + k * kCB < nvn) pre[k] = reinterpret_cast<const uint4 *>(nlo)[threadIdx.x + k * kCB];
-      __syncthreads();                                        // tile t staged
-      store_tile(t, lo);
-      if (!has_next) break;
-      __syncthreads();                                        // tile t consumed
-      {
-        uint4 *d = reinterpret_cast<uint4 *>(stage);
-#pragma unroll
-        for (int k = 0; k < kPre; k++)
-          if (threadIdx.x + k * kCB < nvn) d[threadIdx.x + k * kCB] = pre[k];
-      }
-      t = tn;
-      lo = nlo;
-    }
+    __syncthreads();
+    store_tile(t, lo);
   }
 }
 
@@ -1325,7 +1272,6 @@ struct BlkArgs {
   uint64_t offset, len;
   uint64_t T;              // packed-memory bytes per tile (multiple of 16)
   uint64_t ntiles;
-  int w4;                  // UNPACK: a granule inside one block at a 4-byte-aligned user address is one dwordx4 store
 };
 
 // block holding instance stream byte q
@@ -1516,8 +1462,12 @@ constexpr uint32_t kBlkMaxMap = kBlkMaxT / 64;
 // dwords under each part, funnel-shifts them into place and ORs them in.
 __device__ uint32_t g_blk_dummy[8];
 
-template <bool PACK, int kBlkNG>
+template <bool PACK>
 __global__ void __launch_bounds__(kCB) k_convert_blk(BlkArgs a) {
+  // granules per lane in flight: PACK (the layouts the span kernel does not
+  // take) 2, UNPACK 4 -- measured against 1 / 2 / 4 with a switch since
+  // removed, profiles/r03/convertor_r3.txt
+  constexpr int kBlkNG = PACK ? 2 : 4;
   __shared__ SBlk sb[kBlkCap];
   __shared__ uint16_t smap[kBlkMaxMap];
   __shared__ SpanTile s_t[2 * kSpanBatch];
@@ -1586,7 +1536,7 @@ __global__ void __launch_bounds__(kCB) k_convert_blk(BlkArgs a) {
         }
 #pragma unroll
         for (int k = 0; k < kBlkNG; k++) {
-          if (st[k] == 1 && ((uintptr_t)up[k] & 3) == 0 && a.w4) {
+          if (st[k] == 1 && ((uintptr_t)up[k] & 3) == 0) {
             W4 w;
             w.x = v[k].x; w.y = v[k].y; w.z = v[k].z; w.w = v[k].w;
             *reinterpret_cast<W4 *>(up[k]) = w;
@@ -1887,31 +1837,17 @@ struct ConvEnv {
   // used at datatype creation)
   bool bmap_inst = env_default_on("MX_CONV_BMAP_INST");
 
-  // BLOCK kernel geometry (A/B switches; results are identical):
-  // MX_CONV_BLK_T = largest tile (4096 .. 65536 packed bytes, default 16384),
-  // MX_CONV_BLK_NG = granules per lane in flight (1, 2, 4; default, here 0: 2
-  // for PACK -- layouts the span kernel does not take -- and 4 for UNPACK:
-  // measured, profiles/r03/convertor_r3.txt),
-  // MX_CONV_BLK_W4=0 stores every UNPACK granule in naturally aligned pieces.
+  // MX_CONV_BLK_T = the BLOCK kernels' largest tile (4096 .. 65536 packed
+  // bytes, default 16384; A/B switch; results are identical)
   uint64_t blk_tmax = [] {
     const char *e = getenv("MX_CONV_BLK_T");
     const long v = e ? atol(e) : 16384;
     return (uint64_t)((v >= 4096 && v <= (long)kBlkMaxT && (v & (v - 1)) == 0) ? v : 16384);
   }();
-  int blk_ng = [] {
-    const char *e = getenv("MX_CONV_BLK_NG");
-    const int v = e ? atoi(e) : 0;
-    return (v == 1 || v == 2 || v == 4) ? v : 0;
-  }();
-  int blk_w4 = env_default_on("MX_CONV_BLK_W4");
   // MX_CONV_BLK_SPAN=0 keeps PACK of monotonic layouts on the granule
   // kernel instead of the span-staged one (A/B switch; used when the block
   // table is planned).
   bool blk_span = env_default_on("MX_CONV_BLK_SPAN");
-
-  // MX_CONV_VEC=0 sends single-run layouts to the general kernels instead
-  // (A/B measurement switch; results are identical).
-  bool vec = env_default_on("MX_CONV_VEC");
 
   // MX_CONV_PIPE=0 sends PACK to the one-tile-per-workgroup kernel instead
   // of the pipelined one (A/B switch; results are identical).
@@ -1920,14 +1856,6 @@ struct ConvEnv {
   // MX_CONV_BMAP=0 keeps small irregular instances on the run-walking tile
   // kernels (A/B switch; results are identical).
   bool bmap = env_default_on("MX_CONV_BMAP");
-
-  // MX_CONV_BMAP_PACK=0 sends PACK of small dense instances to the piece
-  // kernel instead of the byte-map kernel (A/B switch).
-  bool bmap_pack = env_default_on("MX_CONV_BMAP_PACK");
-
-  // MX_CONV_PPACK=0 keeps PACK of layouts the byte map does not take on the
-  // run-walking kernels instead of the piece kernel (A/B switch).
-  bool ppack = env_default_on("MX_CONV_PPACK");
 
   // MX_CONV_BMAP_DW=0 gives each lane of the byte-map PACK kernel 16 packed
   // bytes (one 16-byte store) instead of one dword per step (A/B switch).
@@ -1941,18 +1869,6 @@ struct ConvEnv {
     const char *e = getenv("MX_CONV_BLK");
     const int v = e ? atoi(e) : 1;
     return (v >= 0 && v <= 2) ? v : 1;
-  }();
-
-  // MX_CONV_BMAP_PIPE=0 runs the byte-map PACK kernel without the span
-  // prefetch of the next tile (A/B switch; results are identical).
-  bool bmap_pipe = env_default_on("MX_CONV_BMAP_PIPE");
-
-  // MX_CONV_BMAP_ALIGN=16|128: the byte-map PACK stages a tile's user span
-  // from its first 16-byte granule or from the start of that granule's
-  // 128-byte line, so that a wave's 1 KiB loads cover whole lines
-  uint64_t bmap_align = [] {
-    const char *e = getenv("MX_CONV_BMAP_ALIGN");
-    return (uint64_t)((e && atoi(e) == 16) ? 16 : 128);
   }();
 
   // MX_CONV_BMAP_QUAD=0 stages the byte-map PACK's map as one row also where
@@ -2004,41 +1920,12 @@ struct ConvEnv {
     return x == kBmapSpans[0] ? 0 : x == kBmapSpans[2] ? 2 : 1;
   }();
 
-  // MX_CONV_UNPACK_PIPE=1 runs the piece UNPACK kernel with the register
-  // prefetch of the next tile's packed range (A/B switch, off: measured
-  // slower; results are identical).
-  bool unpack_pipe = env_default_off("MX_CONV_UNPACK_PIPE");
-
   // The piece UNPACK form: MX_CONV_UNPACK_DIRECT=0 always the LDS-staged tile
   // kernel (here 1), =1 always one piece per lane (2), unset (0): measured
   // per datatype (mx_ddt::up_choice).  Results are identical.
   int unpack_direct = [] {
     const char *e = getenv("MX_CONV_UNPACK_DIRECT");
     return (e && *e == '0') ? 1 : (e && *e == '1') ? 2 : 0;
-  }();
-
-  // MX_CONV_VEC_SPAN=0 packs periodic small-block vectors through the VEC
-  // kernel instead of k_pack_vec_span (A/B switch; results are identical).
-  bool vec_span = env_default_on("MX_CONV_VEC_SPAN");
-
-  // MX_CONV_PIPE_GEOM selects the pipelined tile PACK's geometry (A/B
-  // measurement; results are identical): 0 = 8192 x 24 KiB span, 1 = 9216 x
-  // 16 KiB, 2 = 9216 x 28 KiB, 3 = 8192 x 16 KiB.  0 is fastest on every type
-  // measured (profiles/r02/convertor_r2.txt): the bank-conflict-free
-  // 36-byte stretches of 1 / 2 lose more to the tile / occupancy change
-  // than the conflicts cost (20k of ~4M cycles per wave).
-  int pipe_geom = [] {
-    const char *e = getenv("MX_CONV_PIPE_GEOM");
-    const int v = e ? atoi(e) : 0;
-    return (v >= 0 && v <= 3) ? v : 0;
-  }();
-
-  // Tile size of the TILE kernels (MX_CONV_TP = 2048 / 4096 / 8192 for
-  // measurement; results are identical).
-  int tile_bytes = [] {
-    const char *e = getenv("MX_CONV_TP");
-    const int v = e ? atoi(e) : 0;
-    return (v == 2048 || v == 4096 || v == 8192) ? v : 8192;
   }();
 };
 
@@ -2226,7 +2113,7 @@ int launch_copy(const Call &c) {
 int launch_vec_span(const Call &c) {
   const DdtLayout &L = c.d->lay;
   const ConvArgs &a = c.a;
-  if (!(a.nruns == 1 && L.runs[0].cnt2 == 1 && !c.d->force_blk && c.env.vec_span)) return kPass;
+  if (!(a.nruns == 1 && L.runs[0].cnt2 == 1 && !c.d->force_blk)) return kPass;
   const DRun &R = L.runs[0];
   // the period: the block stride, or the extent for one block per instance;
   // instances continue it when extent == cnt1 * period, or the window stays
@@ -2262,7 +2149,7 @@ int launch_vec(const Call &c) {
   const DdtLayout &L = c.d->lay;
   const ConvArgs &a = c.a;
   if (!(a.nruns == 1 && L.runs[0].cnt2 == 1 && c.u % 4 == 0 && c.u != 16 && L.runs[0].blen <= kVecMaxBlen &&
-        c.env.vec && !c.d->force_blk))
+        !c.d->force_blk))
     return kPass;
   took(c, PATH_VEC);
   const DRun &R = L.runs[0];
@@ -2312,7 +2199,6 @@ int launch_blk(const Call &c) {
   b.ntiles = ((uintptr_t)a.packed + a.len - MA + b.T - 1) / b.T;
   const unsigned grid = tile_grid(b.ntiles, 8);
   took(c, PATH_BLOCK);
-  b.w4 = c.env.blk_w4;
   if (PACK && bt->Tspan) {
     b.T = bt->Tspan;
     b.ntiles = ((uintptr_t)a.packed + a.len - MA + b.T - 1) / b.T;
@@ -2321,10 +2207,7 @@ int launch_blk(const Call &c) {
     hipLaunchKernelGGL(k_pack_blk_span, dim3(gs), dim3(kCB), lds, c.s, b, bt->capspan);
     return mx_check_launch();
   }
-  const int ng = c.env.blk_ng ? c.env.blk_ng : (PACK ? 2 : 4);
-  if (ng == 1) hipLaunchKernelGGL((k_convert_blk<PACK, 1>), dim3(grid), dim3(kCB), 0, c.s, b);
-  else if (ng == 2) hipLaunchKernelGGL((k_convert_blk<PACK, 2>), dim3(grid), dim3(kCB), 0, c.s, b);
-  else hipLaunchKernelGGL((k_convert_blk<PACK, 4>), dim3(grid), dim3(kCB), 0, c.s, b);
+  hipLaunchKernelGGL(k_convert_blk<PACK>, dim3(grid), dim3(kCB), 0, c.s, b);
   return mx_check_launch();
 }
 
@@ -2353,10 +2236,10 @@ int launch_granule(const Call &c) {
   return mx_check_launch();
 }
 
-template <int SPAN, bool DW, bool PIPE, bool NT>
+template <int SPAN, bool DW, bool NT>
 void launch_bmap_map(bool map16, unsigned grid, size_t lds, hipStream_t s, const BmapArgs &b) {
-  if (map16) hipLaunchKernelGGL((k_pack_bmap<SPAN, uint16_t, DW, PIPE, NT>), dim3(grid), dim3(kCB), lds, s, b);
-  else hipLaunchKernelGGL((k_pack_bmap<SPAN, uint32_t, DW, PIPE, NT>), dim3(grid), dim3(kCB), lds, s, b);
+  if (map16) hipLaunchKernelGGL((k_pack_bmap<SPAN, uint16_t, DW, NT>), dim3(grid), dim3(kCB), lds, s, b);
+  else hipLaunchKernelGGL((k_pack_bmap<SPAN, uint32_t, DW, NT>), dim3(grid), dim3(kCB), lds, s, b);
 }
 
 // small irregular instances, PACK: the byte map (see the kernel)
@@ -2364,8 +2247,7 @@ int launch_bmap(const Call &c) {
   const DdtLayout &L = c.d->lay;
   const ConvArgs &a = c.a;
   const ConvEnv &E = c.env;
-  if (!(!L.bmap.empty() && E.bmap && L.bmap_T && !L.piece_pack && (((uintptr_t)a.packed - a.offset) & 15) == 0 &&
-        E.bmap_pack))
+  if (!(!L.bmap.empty() && E.bmap && L.bmap_T && !L.piece_pack && (((uintptr_t)a.packed - a.offset) & 15) == 0))
     return kPass;
   BmapArgs b;
   b.map = c.d->map_dev;
@@ -2380,7 +2262,7 @@ int launch_bmap(const Call &c) {
   b.offset = a.offset;
   b.len = a.len;
   b.g0 = a.offset / 16;
-  const bool dw = E.bmap_dw, nt = E.bmap_nt, pipe = E.bmap_pipe;
+  const bool dw = E.bmap_dw, nt = E.bmap_nt;
   int si = E.bmap_span_idx;
   const bool word = L.bmap_word && E.bmap_word && dw;
   const size_t map_lds = (word ? L.size / 4 : L.bmap_quad && E.bmap_quad ? 4 * L.size : L.size + 3) * (L.map16 ? 2 : 4);
@@ -2390,7 +2272,7 @@ int launch_bmap(const Call &c) {
   // pack_floor_r5q.txt), 256 MiB: struct 24 KiB 123 us / 12 KiB 159 /
   // 48 KiB 157 (floor 125); indexed 123 / 116 / 180 (floor 109)
   if (si < 0) si = wgs_per_cu(kBmapSpans[1] + 32 + map_lds + 128) >= 5 ? 1 : 0;
-  if (!L.bmap_Ts[si] || !(dw && nt && pipe) || kBmapSpans[si] + 32 + map_lds > 65536)
+  if (!L.bmap_Ts[si] || !(dw && nt) || kBmapSpans[si] + 32 + map_lds > 65536)
     si = 1;                                       // other spans: the default kernel shape only
   b.T = L.bmap_Ts[si];
   b.ntiles = ((a.offset + a.len + 15) / 16 * 16 - b.g0 * 16 + b.T - 1) / b.T;
@@ -2402,15 +2284,12 @@ int launch_bmap(const Call &c) {
   const unsigned grid = tile_grid(b.ntiles, wgs_per_cu(lds));
   b.adv_b = (uint32_t)((kCB * 4) % L.size);
   b.adv_io = (int64_t)((kCB * 4) / L.size) * b.ext;
-  b.lo_mask = E.bmap_align - 1;
   took(c, PATH_BMAP);
-  if (si == 0) launch_bmap_map<kBmapSpans[0], true, true, true>(L.map16, grid, lds, c.s, b);
-  else if (si == 2) launch_bmap_map<kBmapSpans[2], true, true, true>(L.map16, grid, lds, c.s, b);
+  if (si == 0) launch_bmap_map<kBmapSpans[0], true, true>(L.map16, grid, lds, c.s, b);
+  else if (si == 2) launch_bmap_map<kBmapSpans[2], true, true>(L.map16, grid, lds, c.s, b);
   else
     with_flag(dw, [&](auto DW) {
-      with_flag(pipe, [&](auto PIPE) {
-        with_flag(nt, [&](auto NT) { launch_bmap_map<kBmapSpan, DW(), PIPE(), NT()>(L.map16, grid, lds, c.s, b); });
-      });
+      with_flag(nt, [&](auto NT) { launch_bmap_map<kBmapSpan, DW(), NT()>(L.map16, grid, lds, c.s, b); });
     });
   return mx_check_launch();
 }
@@ -2462,7 +2341,7 @@ int launch_piece(const Call &c) {
   mx_ddt *dm = c.d;
   const DdtLayout &L = dm->lay;
   const ConvArgs &a = c.a;
-  if (!(!L.bmap.empty() && c.env.bmap && (!PACK || c.env.ppack))) return kPass;
+  if (L.bmap.empty() || !c.env.bmap) return kPass;
   mx_ddt::PieceTab *pt;
   {
     std::lock_guard<std::mutex> g(dm->mu);
@@ -2503,29 +2382,13 @@ int launch_piece(const Call &c) {
     if (p.ntld) hipLaunchKernelGGL(k_unpack_piece_direct<true>, dim3(g2), dim3(kCB), 0, c.s, p);
     else hipLaunchKernelGGL(k_unpack_piece_direct<false>, dim3(g2), dim3(kCB), 0, c.s, p);
   } else {
-    with_flag(c.env.unpack_pipe, [&](auto PIPE) {
-      with_flag(p.tbl_lds, [&](auto TL) {
-        hipLaunchKernelGGL((k_unpack_piece<PIPE(), TL()>), dim3(grid), dim3(kCB), lds, c.s, p);
-      });
+    with_flag(p.tbl_lds, [&](auto TL) {
+      hipLaunchKernelGGL((k_unpack_piece<TL()>), dim3(grid), dim3(kCB), lds, c.s, p);
     });
   }
   const int lrc = mx_check_launch();
   if (ev1 && hipEventRecord(ev1, c.s) != hipSuccess) (void)hipGetLastError();
   return lrc;
-}
-
-// the pipelined tile PACK at one geometry, wgs workgroups per CU
-template <int TP, int SPAN>
-void launch_pipe_geom(const Call &c, int nlds, size_t rb, int wgs) {
-  const uint64_t tiles = (c.a.len + TP - 1) / TP;
-  hipLaunchKernelGGL((k_pack_tile_pipe<TP, SPAN>), dim3(tile_grid(tiles, wgs)), dim3(kCB), (PipeGeom<TP, SPAN>::lds(rb)),
-                     c.s, c.a, nlds, tiles);
-}
-
-template <bool PACK, int TP>
-void launch_tile_bytes(const Call &c, int nlds, size_t rb, int wordpar) {
-  hipLaunchKernelGGL((k_convert_tile<PACK, TP>), dim3((unsigned)((c.a.len + TP - 1) / TP)), dim3(kCB),
-                     TileGeom<TP>::lds(PACK, rb), c.s, c.a, nlds, wordpar);
 }
 
 // narrow pieces: tile kernels (PACK needs a monotonic layout so that a
@@ -2538,22 +2401,16 @@ int launch_tile(const Call &c) {
   took(c, PATH_TILE);
   const int nlds = a.nruns <= 64 ? 1 : 0;
   const size_t rb = nlds ? (size_t)a.nruns * sizeof(DRun) : 0;
+  const uint64_t tiles = (a.len + kTP - 1) / kTP;
   if (PACK && c.env.pipe) {
-    const int geom = c.env.pipe_geom;
-    if (geom == 2) launch_pipe_geom<9216, 28672>(c, nlds, rb, 3);
-    else if (geom == 3) launch_pipe_geom<8192, 16384>(c, nlds, rb, 6);
-    else if (geom == 1) launch_pipe_geom<9216, 16384>(c, nlds, rb, 6);
-    else launch_pipe_geom<8192, 24576>(c, nlds, rb, 4);
+    hipLaunchKernelGGL(k_pack_tile_pipe, dim3(tile_grid(tiles, kPipeWgs)), dim3(kCB), pipe_lds(rb), c.s, a, nlds, tiles);
     return mx_check_launch();
   }
-  const int tp = c.env.tile_bytes;
   // narrow 4-byte-aligned blocks: word-parallel stores (see the kernel)
   uint64_t maxblen = 0;
   for (const DRun &r : L.runs) maxblen = std::max<uint64_t>(maxblen, r.blen);
   const int wordpar = !PACK && (c.u % 4) == 0 && maxblen <= 32;
-  if (tp == 2048) launch_tile_bytes<PACK, 2048>(c, nlds, rb, wordpar);
-  else if (tp == 4096) launch_tile_bytes<PACK, 4096>(c, nlds, rb, wordpar);
-  else launch_tile_bytes<PACK, 8192>(c, nlds, rb, wordpar);
+  hipLaunchKernelGGL(k_convert_tile<PACK>, dim3((unsigned)tiles), dim3(kCB), tile_lds(PACK, rb), c.s, a, nlds, wordpar);
   return mx_check_launch();
 }
 

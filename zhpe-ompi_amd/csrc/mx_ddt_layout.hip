@@ -216,14 +216,14 @@ void build_bmap(DdtLayout *d, bool inst_tiles) {
     return w;
   };
   // the largest T (a multiple of 256, at most 2/3 of the span) whose worst
-  // user span + 160 fits: the span staged from a 128-byte line start
-  // (MX_CONV_BMAP_ALIGN) plus its 16-byte rounding up.  worst() grows with T.
+  // user span + kBmapSlack fits: the span staged from a line start plus its
+  // 16-byte rounding up.  worst() grows with T.
   for (int k = 0; k < 3; k++) {
     const int64_t span = kBmapSpans[k];
     uint64_t lo = 0, hi = (uint64_t)span * 2 / 3 / 256;      // in units of 256
     while (lo < hi) {
       const uint64_t mid = (lo + hi + 1) / 2;
-      if (worst(mid * 256) + 160 <= span) lo = mid;
+      if (worst(mid * 256) + kBmapSlack <= span) lo = mid;
       else hi = mid - 1;
     }
     d->bmap_Ts[k] = lo * 256;
@@ -232,9 +232,9 @@ void build_bmap(DdtLayout *d, bool inst_tiles) {
     // instance boundary and stages k of them, not the k + 1 a tile cut
     // mid-instance does (indexed: 12.9 instead of 19.3 KiB per 10 KiB of stream)
     if (!d->monotonic && S % 16 == 0) {
-      const int64_t kk = (span - 160 - d->uspan) / ext;   // worst(kk * S) + 160 <= span
+      const int64_t kk = (span - kBmapSlack - d->uspan) / ext;   // worst(kk * S) + kBmapSlack <= span
       if (kk >= 1 && (uint64_t)kk * S >= 256 && (uint64_t)kk * S <= (uint64_t)span * 2 / 3 &&
-          worst((uint64_t)kk * S) + 160 <= span && inst_tiles)
+          worst((uint64_t)kk * S) + kBmapSlack <= span && inst_tiles)
         d->bmap_Ts[k] = (uint64_t)kk * S;
     }
   }

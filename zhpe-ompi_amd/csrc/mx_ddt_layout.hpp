@@ -41,7 +41,13 @@ constexpr uint32_t kBmapMaxS = 65535;      // packed bytes per instance (piece s
 constexpr size_t kBmapLds = 20480;         // PACK: map bytes staged in LDS
 constexpr int kBmapSpan = 24576;           // PACK: user span staged per tile
 constexpr int kBmapSpans[3] = {12288, kBmapSpan, 49152};   // MX_CONV_BMAP_SPAN choices
-constexpr int kPieceStage = 16384;         // UNPACK: packed bytes staged per tile
+// PACK: a tile's staged span starts at the 128-byte line holding its first
+// user byte (a wave's 1 KiB loads then cover whole lines) and ends on the
+// 16-byte granule after its last one, so a tile of w user bytes stages less
+// than w + kBmapAlign + 16 bytes; the planner leaves one more granule to spare
+constexpr int kBmapAlign = 128;
+constexpr int kBmapSlack = kBmapAlign + 32;
+constexpr int kPieceStage = 16384;        // UNPACK: packed bytes staged per tile
 
 struct DPiece {
   int32_t uoff;       // user offset from the instance origin
