@@ -15,6 +15,13 @@
  *                         456-623, 132-) + tuned rule (decision_fixed.c:466-512)
  *   mx_allgather       <- coll_base_allgather.c (pure data movement)
  *   mx_bcast           <- coll_base_bcast.c (pure data movement)
+ *   mx_alltoall        <- coll_base_alltoall.c:132-, 569- (pairwise, linear)
+ *   mx_alltoallv       <- coll_base_alltoallv.c:125-, 189-
+ *   mx_allgatherv      <- coll_base_allgatherv.c:93-579
+ *                         (pure data movement: every reference algorithm
+ *                         gives the same bytes; one exchange kernel moves a
+ *                         table of {src, dst, bytes} jobs of any size and
+ *                         byte alignment, csrc/mx_exchange.hip)
  *
  * Design (MI355X-first, not the reference's message pattern):
  *  * data moves ALL-PEER over xGMI in one step per phase (every GPU writes
@@ -295,6 +302,50 @@ int mx_reduce_scatter(mx_comm_t *comm, const void *sbuf, void *rbuf,
 int mx_allgather(mx_comm_t *comm, const void *sbuf, void *rbuf, size_t bytes, void *stream);
 int mx_bcast(mx_comm_t *comm, void *buf, size_t bytes, int root, void *stream);
 
+/* Exchanges (slots `alltoall`, `alltoallv`, `allgatherv`, coll.h:204-211).
+ * Sizes are bytes and displacements byte offsets, in arrays of `size`
+ * entries; buffers may have any byte alignment.  Blocking like mx_allgather;
+ * size 1 is a device copy.
+ *   mx_alltoall    block p of sbuf (sbuf + p*bytes) goes to rank p; rank r's
+ *                  block lands at rbuf + r*bytes.
+ *   mx_alltoallv   sbytes[p] bytes at sbuf + soffs[p] go to rank p; rank p's
+ *                  bytes land at rbuf + roffs[p].  A sender that announces
+ *                  more than rbytes[p] is cut at rbytes[p]: nothing past it
+ *                  is written.  Needs the communicator's registration page
+ *                  (the ranks publish their send rows there): without it the
+ *                  call returns MX_ERR_UNSUPPORTED on every rank.
+ *   mx_allgatherv  rank p's rbytes[p] bytes land at rbuf + roffs[p] on every
+ *                  rank; sbytes is this rank's rbytes[rank].
+ * sbuf MX_IN_PLACE follows MPI (on every rank or on none; alltoallv checks
+ * it): alltoall / alltoallv send from and receive into rbuf with the receive
+ * sizes and offsets; allgatherv finds its own block already at rbuf +
+ * roffs[rank].  A rank of alltoallv / allgatherv that sends nothing may pass
+ * any sbuf, NULL included, and one that receives nothing any rbuf: the data
+ * path never depends on one rank's buffers alone.
+ * Data path: calls of mx_comm_set_reg_min bytes and more pull every block
+ * straight from the peers' registered sbufs (zero-copy; remote reads, local
+ * writes); smaller calls, in-place calls and calls whose registration is
+ * refused go through the staging in rounds (mx_comm_exchange_stats).
+ * Like the registration exchange, mx_alltoallv's row exchange is a host wait
+ * for every rank, bounded only by mx_comm_set_timeout (default for a
+ * communicator made here: 60 s; 0 = forever): a rank that leaves the call
+ * early -- a rank-local MX_ERR_ARG is returned before it -- keeps its peers
+ * there until then, after which the communicator is poisoned. */
+int mx_alltoall(mx_comm_t *comm, const void *sbuf, void *rbuf, size_t bytes, void *stream);
+int mx_alltoallv(mx_comm_t *comm, const void *sbuf, const size_t *sbytes, const size_t *soffs, void *rbuf,
+                 const size_t *rbytes, const size_t *roffs, void *stream);
+int mx_allgatherv(mx_comm_t *comm, const void *sbuf, size_t sbytes, void *rbuf, const size_t *rbytes,
+                  const size_t *roffs, void *stream);
+/* out: [0] exchange calls (the three above and their _local forms),
+ * [1] zero-copy calls, [2] staged calls, [3] staged rounds.  comm NULL: the
+ * sums over every communicator this process has had. */
+int mx_comm_exchange_stats(mx_comm_t *comm, uint64_t out[4]);
+/* mx_alltoallv calls whose `size` x largest pair (of any rank; known after
+ * the row exchange, so the same on every rank) is at most min_bytes return
+ * MX_ERR_UNSUPPORTED on every rank, for a caller with a cheaper route for
+ * small calls and no size of its own that all ranks share.  0 = never. */
+int mx_comm_set_exchange_min(mx_comm_t *comm, size_t min_bytes);
+
 /* Rooted reduce (coll slot `reduce`, coll.h:239-241): the result lands in
  * rbuf on `root` only (rbuf may be NULL elsewhere); sbuf MPI_IN_PLACE on
  * the root.  Bit-identical to the reference algorithm `alg` (the tree of
@@ -536,6 +587,19 @@ int mx_reduce_scatter_local(mx_comm_t *comm, const void *const *sbufs, void *con
 int mx_allgather_local(mx_comm_t *comm, const void *const *sbufs, void *const *rbufs,
                        size_t bytes, void *stream);
 int mx_bcast_local(mx_comm_t *comm, void *const *bufs, size_t bytes, int root, void *stream);
+/* Exchanges, each ONE launch of the exchange kernel.  sbufs NULL or
+ * sbufs[j] == MX_IN_PLACE: rank j is in place (MPI: all ranks or none).
+ * mx_alltoallv_local takes the size x size matrices, row = the rank that
+ * owns the buffer: sbytes[i*size+j] bytes at sbufs[i] + soffs[i*size+j] go
+ * to rbufs[j] + roffs[j*size+i], cut at rbytes[j*size+i].  In place the
+ * receive matrices describe both sides, and the receive ranges of one
+ * buffer must not overlap (MPI) -- the launch reads them while it writes
+ * them, so it goes through a temporary copy of the sent ranges. */
+int mx_alltoall_local(mx_comm_t *comm, const void *const *sbufs, void *const *rbufs, size_t bytes, void *stream);
+int mx_alltoallv_local(mx_comm_t *comm, const void *const *sbufs, const size_t *sbytes, const size_t *soffs,
+                       void *const *rbufs, const size_t *rbytes, const size_t *roffs, void *stream);
+int mx_allgatherv_local(mx_comm_t *comm, const void *const *sbufs, void *const *rbufs, const size_t *rbytes,
+                        const size_t *roffs, void *stream);
 int mx_reduce_local(mx_comm_t *comm, const void *const *sbufs, void *const *rbufs, size_t count,
                     int type, int op, int root, int alg, void *stream);
 int mx_scan_local(mx_comm_t *comm, const void *const *sbufs, void *const *rbufs, size_t count,

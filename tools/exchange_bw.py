@@ -1,0 +1,112 @@
+#!/usr/bin/env python3
+"""Call rates of the exchange kernel on a local communicator (8 ranks on one
+GPU), against the existing copy kernel in the same run.
+
+Per pair size S (4 KiB ... 32 MiB) four calls are timed:
+  (a) alltoall_local, every buffer 16-byte aligned
+  (b) alltoallv_local with S-byte pairs whose sources sit 4 bytes off their
+      destinations' alignment (the dword-shift path)
+  (c) alltoallv_local with pair sizes spread 1 : 64 around S
+  (d) allgather_local of S bytes per rank: the same n*n*S bytes through
+      k_copy, the yardstick
+Times are host-clock medians of blocking calls (each ends in a stream
+synchronise), so small sizes measure launch and synchronise cost.  GB/s is
+read + write traffic (2 x payload) over call time; the share is of the
+6.29 TB/s float4 copy rate measured for this part.
+
+    python tools/exchange_bw.py [--out profiles/r07/exchange_local.txt]
+"""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "zhpe-ompi_amd"))
+
+COPY_RATE = 6.29e12
+N = 8
+
+
+def _time(fn, payload):
+    import torch
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    est = max(time.perf_counter() - t0, 1e-6)
+    reps = int(min(200, max(7, 0.3 / est)))
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        ts.append(time.perf_counter() - t0)
+    t = statistics.median(ts)
+    return t, 2 * payload / t / 1e9
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import torch
+    import mxompi
+    if not torch.cuda.is_available():
+        sys.exit("exchange_bw: no GPU")
+    mxompi.init(0)
+    comm = mxompi.Comm.local(N)
+    st = torch.cuda.current_stream().cuda_stream
+    lines = [f"# exchange_bw: local communicator, n = {N}, {torch.cuda.get_device_name(0)}",
+             "# GB/s = 2 x payload / median call time (host clock, blocking calls); "
+             "share = of 6.29 TB/s (float4 copy)",
+             f"{'pair':>10} {'case':<28} {'payload MiB':>12} {'us':>10} {'GB/s':>9} {'vs (d)':>7} {'share':>6}"]
+    sizes = [4 << 10, 32 << 10, 256 << 10, 2 << 20, 16 << 20, 32 << 20]
+    for S in sizes:
+        spread = [[max(16, (S >> 3) << ((i + j) % 7)) for j in range(N)] for i in range(N)]   # S/8 ... 8S
+        span = max(N * S, max(sum(r) for r in spread),
+                   max(sum(spread[i][j] for i in range(N)) for j in range(N))) + 64
+        sb = [torch.empty(span, dtype=torch.uint8, device="cuda").random_(0, 256) for _ in range(N)]
+        rb = [torch.empty(span, dtype=torch.uint8, device="cuda") for _ in range(N)]
+        # tables and pointer arrays are converted once: the timed calls are the library's
+        sp, rp = mxompi._ptrs([t.data_ptr() for t in sb]), mxompi._ptrs([t.data_ptr() for t in rb])
+        eq = [S] * (N * N)
+        off = [j * S for _ in range(N) for j in range(N)]
+        off4 = [j * S + 4 for _ in range(N) for j in range(N)]
+        vs = [v for r in spread for v in r]
+        vso = [sum(spread[i][:j]) for i in range(N) for j in range(N)]
+        vr = [spread[i][j] for j in range(N) for i in range(N)]
+        vro = [sum(spread[k][j] for k in range(i)) for j in range(N) for i in range(N)]
+        ceq, coff, coff4 = mxompi._sizes(eq), mxompi._sizes(off), mxompi._sizes(off4)
+        cvs, cvso, cvr, cvro = mxompi._sizes(vs), mxompi._sizes(vso), mxompi._sizes(vr), mxompi._sizes(vro)
+        cases = [
+            ("(d) allgather_local (k_copy)", lambda: comm.allgather_local(sp, rp, S, st), N * N * S),
+            ("(a) alltoall aligned", lambda: comm.alltoall_local(sp, rp, S, st), N * N * S),
+            ("(b) alltoall src +4 bytes", lambda: comm.alltoallv_local(sp, ceq, coff4, rp, ceq, coff, st), N * N * S),
+            ("(c) alltoallv 1:64 spread", lambda: comm.alltoallv_local(sp, cvs, cvso, rp, cvr, cvro, st), sum(vs)),
+        ]
+        ref = None
+        for name, fn, payload in cases:
+            t, gbs = _time(fn, payload)
+            if ref is None:
+                ref = gbs
+            lines.append(f"{S:>10} {name:<28} {payload / 2**20:>12.2f} {t * 1e6:>10.1f} {gbs:>9.1f} "
+                         f"{gbs / ref:>7.2f} {100 * gbs * 1e9 / COPY_RATE:>5.1f}%")
+        # the timed calls moved the right bytes (the last one: the spread alltoallv)
+        got = rb[1][vro[N + 0]:vro[N + 0] + spread[0][1]]
+        want = sb[0][vso[1]:vso[1] + spread[0][1]]
+        assert torch.equal(got, want), "alltoallv moved wrong bytes"
+        del sb, rb
+        torch.cuda.empty_cache()
+    comm.close()
+    text = "\n".join(lines) + "\n"
+    print(text, end="")
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(text)
+
+
+if __name__ == "__main__":
+    main()

@@ -54,6 +54,7 @@
 #include "mx_comm.hpp"
 #include "../../include/mx_convertor.h"
 #include "mx_env.hpp"
+#include "mx_exchange.hpp"
 
 namespace mx {
 
@@ -354,6 +355,17 @@ struct RegRec {
 static_assert(sizeof(RegRec) == 256, "RegRec layout");
 static_assert(std::atomic<uint64_t>::is_always_lock_free, "shared-memory atomics");
 
+// The page: two banks of records (reg_exchange), then the row area of
+// alltoallv (xrow_exchange): every rank publishes the row it sends by, (offsets, sizes) -- one
+// host round like tune_exchange.
+// Two banks, call k in bank k % 2, for the reason reg_exchange gives.
+struct XRow {
+  std::atomic<uint64_t> seq;
+  uint64_t flags;   // bits 0-3: the send buffer's address mod 16; bit 4: the rank calls in place
+  uint64_t bytes[MAXR], offs[MAXR];
+};
+static size_t reg_page_bytes(int n) { return 2 * (size_t)n * sizeof(RegRec) + 2 * (size_t)n * sizeof(XRow); }
+
 // bytes per rank (MX_REG_MIN overrides; 0 = off): zero-copy is ahead of the
 // staged path at every size measured above the one-shot range
 constexpr size_t kRegMinDefault = (size_t)256 << 10;
@@ -380,6 +392,15 @@ static std::mutex g_live_mu;
 static std::vector<mx_comm *> g_live;
 struct Deferred { void *p; int kind; };
 static std::vector<Deferred> g_graveyard;
+
+// exchange counters (mx_comm_exchange_stats): per communicator and, for a
+// caller that cannot reach the communicator (an MPI program above the coll
+// component), summed over the process
+static std::atomic<uint64_t> g_xst[4];
+static void xcount(mx_comm *c, int k) {
+  c->xst[k]++;
+  g_xst[k].fetch_add(1, std::memory_order_relaxed);
+}
 
 static void live_add(mx_comm *c) {
   std::lock_guard<std::mutex> lk(g_live_mu);
@@ -536,7 +557,7 @@ static void reg_create(mx_comm *c, char *name, size_t cap) {
   name[0] = 0;
   if (c->size < 2 || !reg_min()) return;
   snprintf(name, cap, "/mx_reg_%d_%u", (int)getpid(), ctr.fetch_add(1));
-  const size_t bytes = 2 * (size_t)c->size * sizeof(RegRec);   // two banks (reg_exchange)
+  const size_t bytes = reg_page_bytes(c->size);
   const int fd = shm_open(name, O_CREAT | O_EXCL | O_RDWR, 0600);
   if (fd < 0) { name[0] = 0; return; }
   void *p = MAP_FAILED;
@@ -550,7 +571,7 @@ static void reg_create(mx_comm *c, char *name, size_t cap) {
 
 static void reg_open(mx_comm *c, const char *name) {
   if (c->reg_shm || !name[0]) return;
-  const size_t bytes = 2 * (size_t)c->size * sizeof(RegRec);
+  const size_t bytes = reg_page_bytes(c->size);
   const int fd = shm_open(name, O_RDWR, 0600);
   if (fd < 0) return;
   void *p = mmap(nullptr, bytes, PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
@@ -1069,6 +1090,7 @@ extern "C" int mx_comm_destroy(mx_comm_t *c) {
   if (c->tail) (void)hipEventDestroy(c->tail);
   reg_release(c);
   p2p_release(c);
+  xtable_free(c->xtab);   // waits for its slots' last launches, then returns them to the pools
   free(c);
   release_flush();
   return MX_SUCCESS;
@@ -1340,6 +1362,96 @@ extern "C" int mx_bcast_local(mx_comm_t *c, void *const *bufs, size_t bytes, int
   int rc = copy_launch(c, a, s);
   if (rc) return rc;
   return finish(c, s);
+}
+
+// Exchanges: the n x n jobs of the call in ONE launch of k_exchange
+// (mx_exchange.hip).  Jobs are listed source by source, so neighbours in the
+// table go to different ranks.
+extern "C" int mx_alltoallv_local(mx_comm_t *c, const void *const *sbufs, const size_t *sbytes, const size_t *soffs,
+                                  void *const *rbufs, const size_t *rbytes, const size_t *roffs, void *stream) {
+  if (!c || !c->local || !rbufs || !rbytes || !roffs) return MX_ERR_ARG;
+  const int n = c->size;
+  const bool inplace = !sbufs || sbufs[0] == MX_IN_PLACE;
+  if (!inplace && (!sbytes || !soffs)) return MX_ERR_ARG;
+  for (int i = 0; i < n; i++) {
+    if (int rc = xcheck_row(n, rbytes + (size_t)i * n, roffs + (size_t)i * n)) return rc;
+    if (!inplace && xcheck_row(n, sbytes + (size_t)i * n, soffs + (size_t)i * n)) return MX_ERR_ARG;
+    if (inplace && !xranges_disjoint(n, rbytes + (size_t)i * n, roffs + (size_t)i * n)) return MX_ERR_ARG;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  if (int orc = order(c, s)) return orc;
+  xcount(c, 0);
+  std::vector<XJob> jobs;
+  jobs.reserve((size_t)n * n);
+  for (int i = 0; i < n; i++)
+    for (int j = 0; j < n; j++) {
+      const size_t ij = (size_t)i * n + j, ji = (size_t)j * n + i;
+      const size_t len = std::min(inplace ? rbytes[ij] : sbytes[ij], rbytes[ji]);   // never past the receiver's size
+      const char *src = inplace ? (const char *)rbufs[i] + roffs[ij] : (const char *)sbufs[i] + soffs[ij];
+      char *dst = (char *)rbufs[j] + roffs[ji];
+      if (len && src != dst) jobs.push_back(XJob{src, dst, len});
+    }
+  if (jobs.size() > (size_t)kXInline && !c->xtab) c->xtab = xtable_new();   // null: launches of kXInline jobs
+  char *tmp = nullptr;
+  int rc = MX_SUCCESS;
+  if (inplace && !jobs.empty()) {
+    // every range is read and overwritten by the same launch: the sent
+    // ranges go through a temporary copy first (each keeps its misalignment)
+    size_t total = 0;
+    std::vector<XJob> first = jobs;
+    for (XJob &jb : first) total += (jb.bytes + 15) / 16 * 16 + 16;
+    if (hipMallocAsync((void **)&tmp, total, s) != hipSuccess) return MX_ERR_NOMEM;
+    size_t o = 0;
+    for (size_t q = 0; q < jobs.size(); q++) {
+      first[q].dst = tmp + o + ((uintptr_t)jobs[q].src & 15);
+      jobs[q].src = first[q].dst;
+      o += (jobs[q].bytes + 15) / 16 * 16 + 16;
+    }
+    rc = exchange_launch(first.data(), first.size(), c->poison, s, c->xtab);
+  }
+  if (!rc) rc = exchange_launch(jobs.data(), jobs.size(), c->poison, s, c->xtab);
+  if (tmp) (void)hipFreeAsync(tmp, s);
+  if (rc) return rc;
+  return finish(c, s);
+}
+
+extern "C" int mx_alltoall_local(mx_comm_t *c, const void *const *sbufs, void *const *rbufs, size_t bytes,
+                                 void *stream) {
+  if (!c || !c->local) return MX_ERR_ARG;
+  const int n = c->size;
+  if ((size_t)n * bytes / (size_t)n != bytes) return MX_ERR_ARG;
+  std::vector<size_t> len((size_t)n * n, bytes), off((size_t)n * n);
+  for (int i = 0; i < n; i++)
+    for (int j = 0; j < n; j++) off[(size_t)i * n + j] = (size_t)j * bytes;
+  return mx_alltoallv_local(c, sbufs, len.data(), off.data(), rbufs, len.data(), off.data(), stream);
+}
+
+extern "C" int mx_allgatherv_local(mx_comm_t *c, const void *const *sbufs, void *const *rbufs, const size_t *rbytes,
+                                   const size_t *roffs, void *stream) {
+  if (!c || !c->local || !rbufs) return MX_ERR_ARG;
+  const int n = c->size;
+  if (int rc = xcheck_row(n, rbytes, roffs)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if (int orc = order(c, s)) return orc;
+  xcount(c, 0);
+  std::vector<XJob> jobs;
+  jobs.reserve((size_t)n * n);
+  for (int i = 0; i < n; i++) {
+    const char *src = (sbufs && sbufs[i] != MX_IN_PLACE) ? (const char *)sbufs[i] : (const char *)rbufs[i] + roffs[i];
+    for (int j = 0; j < n; j++) {
+      char *dst = (char *)rbufs[j] + roffs[i];
+      if (rbytes[i] && src != dst) jobs.push_back(XJob{src, dst, rbytes[i]});
+    }
+  }
+  if (jobs.size() > (size_t)kXInline && !c->xtab) c->xtab = xtable_new();
+  if (int rc = exchange_launch(jobs.data(), jobs.size(), c->poison, s, c->xtab)) return rc;
+  return finish(c, s);
+}
+
+extern "C" int mx_comm_exchange_stats(mx_comm_t *c, uint64_t out[4]) {
+  if (!out) return MX_ERR_ARG;
+  for (int k = 0; k < 4; k++) out[k] = c ? c->xst[k] : g_xst[k].load(std::memory_order_relaxed);
+  return MX_SUCCESS;
 }
 
 // ---------------------------------------------------------------------------
@@ -2199,6 +2311,264 @@ static int allgather_impl(mx_comm_t *c, const void *sbuf, void *rbuf, size_t byt
     if ((rc = signal_done(c, g, s, o + cb >= bytes ? &dm : nullptr))) return rc;
   }
   return finish_done(c, s, dm);
+}
+
+// ---------------------------------------------------------------------------
+// exchanges: alltoall, alltoallv, allgatherv (k_exchange, mx_exchange.hip)
+// ---------------------------------------------------------------------------
+namespace {
+
+// One rank's view of an exchange.  Every field but the buffers is known to
+// -- and equal on -- every rank that needs it: the collective decisions
+// (data path, round count) depend only on zc_bytes, max_pair and inplace.
+struct XCall {
+  const char *sb;              // what this rank sends from (in place: its rbuf)
+  char *rb;
+  size_t sb_span, rb_span;     // bytes of sb / rb the call may touch (registration)
+  size_t send_off[MAXR], send_len[MAXR];   // my block for p, in sb
+  size_t pull_off[MAXR];       // my block in p's sb
+  size_t mis, peer_mis[MAXR];  // sb's address mod 16, mine and p's, where the ranks exchanged it (else 0)
+  size_t recv_off[MAXR], recv_len[MAXR];   // where p's block lands in rb; what of it is taken
+  size_t max_pair;             // the largest block any rank sends
+  size_t zc_bytes;             // the size the zero-copy threshold sees
+  bool inplace;
+};
+
+
+static int xrow_exchange(mx_comm *c, const size_t *bytes, const size_t *offs, uint64_t flags, const XRow **rows) {
+  const int n = c->size;
+  const uint64_t k = ++c->xrow_seq;
+  XRow *X = (XRow *)((char *)c->reg_shm + 2 * (size_t)n * sizeof(RegRec)) + (k & 1) * (size_t)n;
+  XRow &me = X[c->rank];
+  me.flags = flags;
+  for (int p = 0; p < n; p++) {
+    me.bytes[p] = bytes[p];
+    me.offs[p] = offs[p];
+  }
+  me.seq.store(k, std::memory_order_release);
+  const auto t0 = std::chrono::steady_clock::now();
+  for (int p = 0; p < n; p++) {
+    unsigned spins = 0;
+    while (X[p].seq.load(std::memory_order_acquire) < k) {
+      if (++spins > 256) {
+        sched_yield();
+        if (c->timeout_s > 0 && secs_since(t0) > c->timeout_s) {
+          c->poisoned = MX_ERR_TIMEOUT;
+          timeout_dump(c, "alltoallv rows");
+          return MX_ERR_TIMEOUT;
+        }
+      }
+    }
+  }
+  *rows = X;
+  return MX_SUCCESS;
+}
+
+static int exchange_mp(mx_comm *c, const XCall &x, hipStream_t s) {
+  DoneMark dm;   // the call's last DONE signal raises the completion word
+  done_mark_arm(c, dm);
+  const int n = c->size, r = c->rank;
+  xcount(c, 0);
+  if (!x.max_pair) return MX_SUCCESS;   // nothing moves on any rank
+  const size_t self_len = std::min(x.send_len[r], x.recv_len[r]);
+  XJob jobs[MAXR];
+  int nj, rc;
+  if (!x.inplace && zc_allowed(c, ZC_DEFAULT, x.zc_bytes)) {
+    // zero-copy: rank r pulls its block from every peer's registered sbuf
+    // straight into its rbuf (remote reads, local writes only).  The kernel
+    // takes any pair of alignments, so the ranks need not agree on one.
+    const char *ps[MAXR];
+    char *pr[MAXR];
+    const int zc = reg_exchange(c, x.sb, x.sb_span, x.rb, x.rb_span, 0, true, ps, pr);
+    if (zc < 0) return zc;
+    if (zc) {
+      const uint64_t g = ++c->gen;
+      xcount(c, 1);
+      if ((rc = signal_wait_all(c, FLAG_READY, g << 1, g << 1, s))) return rc;   // every sbuf holds its blocks
+      nj = 0;
+      for (int p = 0; p < n; p++)
+        if (p != r) jobs[nj++] = XJob{ps[p] + x.pull_off[p], x.rb + x.recv_off[p], x.recv_len[p]};
+      if (x.sb + x.send_off[r] != x.rb + x.recv_off[r])
+        jobs[nj++] = XJob{x.sb + x.send_off[r], x.rb + x.recv_off[r], self_len};
+      if ((rc = exchange_launch(jobs, nj, c->poison, s))) return rc;
+      if ((rc = signal_wait_all(c, FLAG_PUSHED, g, g, s))) return rc;   // done reading the peers' sbufs
+      if ((rc = signal_done(c, g, s, &dm))) return rc;
+      return finish_done(c, s, dm);
+    }
+  }
+  // staged: n slots; the sender pushes its block for p into p's slot r, and
+  // after READY the receiver moves slot p to its place in rbuf.  A slot
+  // offset keeps the source address mod 16, so the push needs no shifting:
+  // exactly where the ranks exchanged their buffers' misalignment
+  // (alltoallv); alltoall and allgatherv exchange nothing, both sides take
+  // the block's offset in the sender's buffer mod 16, which is the address's
+  // for a 16-byte aligned sbuf -- a misaligned one pushes through the
+  // kernel's shift path (correct, slower).
+  // In place the pushes read what the moves overwrite: a rank's moves follow
+  // its own pushes on the stream and every peer's pushes through READY.
+  size_t slot, cap;
+  if (!xstage_slots(c->main_bytes, n, &slot, &cap)) return MX_ERR_NOMEM;
+  const uint64_t rounds = xrounds(x.max_pair, cap);
+  xcount(c, 2);
+  for (uint64_t q = 0; q < rounds; q++) {
+    const uint64_t g = ++c->gen;
+    size_t o, l;
+    xcount(c, 3);
+    if ((rc = wait_all(c, FLAG_DONE, g - 1, s))) return rc;
+    nj = 0;
+    for (int p = 0; p < n; p++) {
+      if (p == r) continue;
+      xround_piece(x.send_len[p], cap, q, &o, &l);
+      jobs[nj++] = XJob{x.sb + x.send_off[p] + o, c->peer_staging[p] + (size_t)r * slot + ((x.mis + x.send_off[p] + o) & 15), l};
+    }
+    xround_piece(self_len, cap, q, &o, &l);
+    if (x.sb + x.send_off[r] != x.rb + x.recv_off[r])
+      jobs[nj++] = XJob{x.sb + x.send_off[r] + o, x.rb + x.recv_off[r] + o, l};
+    if ((rc = exchange_launch(jobs, nj, c->poison, s))) return rc;
+    if ((rc = signal_wait_all(c, FLAG_READY, g << 1, g << 1, s))) return rc;
+    nj = 0;
+    for (int p = 0; p < n; p++) {
+      if (p == r) continue;
+      xround_piece(x.recv_len[p], cap, q, &o, &l);
+      jobs[nj++] = XJob{c->staging + (size_t)p * slot + ((x.peer_mis[p] + x.pull_off[p] + o) & 15), x.rb + x.recv_off[p] + o, l};
+    }
+    if ((rc = exchange_launch(jobs, nj, c->poison, s))) return rc;
+    if ((rc = signal_done(c, g, s, q + 1 == rounds ? &dm : nullptr))) return rc;
+  }
+  return finish_done(c, s, dm);
+}
+
+// the common prologue: a communicator of one process (local, size 1) or of
+// one rank is served by the caller with a device copy
+static int exchange_enter(mx_comm *c, hipStream_t s) {
+  if (int orc = order(c, s)) return orc;
+  if (c->size > 1 && !(c->flags & MX_COMM_IPC)) return MX_ERR_STATE;
+  return MX_SUCCESS;
+}
+static int exchange_self(mx_comm *c, const char *src, char *dst, size_t bytes, hipStream_t s) {
+  xcount(c, 0);
+  if (bytes && src != dst) {
+    const XJob jb{src, dst, bytes};
+    if (int rc = exchange_launch(&jb, 1, c->poison, s)) return rc;
+  }
+  return finish(c, s);
+}
+
+}  // namespace
+
+extern "C" int mx_comm_set_exchange_min(mx_comm_t *c, size_t min_bytes) {
+  if (!c) return MX_ERR_ARG;
+  c->xmin = min_bytes;
+  return MX_SUCCESS;
+}
+
+extern "C" long long mx_comm_exchange_rounds(const mx_comm_t *c, size_t max_pair) {
+  if (!c) return MX_ERR_ARG;
+  if (c->local || c->size < 2) return 0;
+  size_t slot, cap;
+  if (!xstage_slots(c->main_bytes, c->size, &slot, &cap)) return MX_ERR_NOMEM;
+  return (long long)xrounds(max_pair, cap);
+}
+
+extern "C" int mx_alltoall(mx_comm_t *c, const void *sbuf, void *rbuf, size_t bytes, void *stream) {
+  if (!c || !rbuf || (c->local && c->size != 1)) return c && c->local ? MX_ERR_STATE : MX_ERR_ARG;
+  const int n = c->size, r = c->rank;
+  if ((size_t)n * bytes / (size_t)n != bytes) return MX_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = exchange_enter(c, s)) return rc;
+  XCall x;
+  memset(&x, 0, sizeof x);
+  x.inplace = sbuf == MX_IN_PLACE || !sbuf;   // every rank sends `bytes`: NULL can only mean in place
+  x.rb = (char *)rbuf;
+  x.sb = x.inplace ? (const char *)rbuf : (const char *)sbuf;
+  if (n == 1) return exchange_self(c, x.sb, x.rb, bytes, s);
+  x.sb_span = x.rb_span = (size_t)n * bytes;
+  for (int p = 0; p < n; p++) {
+    x.send_off[p] = x.recv_off[p] = (size_t)p * bytes;
+    x.pull_off[p] = (size_t)r * bytes;
+    x.send_len[p] = x.recv_len[p] = bytes;
+  }
+  x.max_pair = bytes;
+  x.zc_bytes = (size_t)n * bytes;
+  return exchange_mp(c, x, s);
+}
+
+extern "C" int mx_allgatherv(mx_comm_t *c, const void *sbuf, size_t sbytes, void *rbuf, const size_t *rbytes,
+                             const size_t *roffs, void *stream) {
+  if (!c || !rbuf || (c->local && c->size != 1)) return c && c->local ? MX_ERR_STATE : MX_ERR_ARG;
+  const int n = c->size, r = c->rank;
+  if (int rc = xcheck_row(n, rbytes, roffs)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = exchange_enter(c, s)) return rc;
+  XCall x;
+  memset(&x, 0, sizeof x);
+  // a rank with an empty block may pass any sbuf, NULL included, without
+  // being in place: the data path must not depend on it (NULL with a block
+  // to send is the other entry points' synonym of MX_IN_PLACE)
+  x.inplace = sbuf == MX_IN_PLACE || (!sbuf && rbytes[r] != 0);
+  x.rb = (char *)rbuf;
+  // in place a rank's block sits at roffs[rank] of its rbuf, on every rank
+  x.sb = (x.inplace || !sbuf) ? (const char *)rbuf : (const char *)sbuf;
+  const size_t mine = x.inplace ? rbytes[r] : std::min(sbytes, rbytes[r]);
+  if (n == 1) return exchange_self(c, x.sb + (x.inplace ? roffs[0] : 0), x.rb + roffs[0], mine, s);
+  for (int p = 0; p < n; p++) {
+    x.send_off[p] = x.inplace ? roffs[r] : 0;
+    x.send_len[p] = mine;
+    x.pull_off[p] = x.inplace ? roffs[p] : 0;
+    x.recv_off[p] = roffs[p];
+    x.recv_len[p] = p == r ? mine : rbytes[p];
+    x.rb_span = std::max(x.rb_span, roffs[p] + rbytes[p]);
+    x.max_pair = std::max(x.max_pair, rbytes[p]);
+    x.zc_bytes += rbytes[p];
+  }
+  x.sb_span = x.inplace ? x.rb_span : mine;
+  return exchange_mp(c, x, s);
+}
+
+extern "C" int mx_alltoallv(mx_comm_t *c, const void *sbuf, const size_t *sbytes, const size_t *soffs, void *rbuf,
+                            const size_t *rbytes, const size_t *roffs, void *stream) {
+  if (!c || (c->local && c->size != 1)) return c && c->local ? MX_ERR_STATE : MX_ERR_ARG;
+  const int n = c->size, r = c->rank;
+  if (int rc = xcheck_row(n, rbytes, roffs)) return rc;
+  XCall x;
+  memset(&x, 0, sizeof x);
+  // Only MX_IN_PLACE is in place here: a rank that sends nothing may pass any
+  // sbuf, NULL included, and one that receives nothing any rbuf, and the
+  // data path must not depend on either (every rank has to choose alike)
+  x.inplace = sbuf == MX_IN_PLACE;
+  if (x.inplace) { sbytes = rbytes; soffs = roffs; }   // MPI: the receive row describes both sides
+  else if (int rc = xcheck_row(n, sbytes, soffs)) return rc;
+  size_t stotal = 0, rtotal = 0;
+  for (int p = 0; p < n; p++) { stotal += sbytes[p]; rtotal += rbytes[p]; }
+  if ((!rbuf && rtotal) || (!x.inplace && !sbuf && stotal)) return MX_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = exchange_enter(c, s)) return rc;
+  x.rb = (char *)rbuf;
+  x.sb = x.inplace ? (const char *)rbuf : (const char *)sbuf;
+  if (!x.sb) x.sb = x.rb;     // nothing to send: any address serves (no byte of it is read)
+  if (!x.rb) x.rb = (char *)x.sb;
+  if (n == 1) return exchange_self(c, x.sb + soffs[0], x.rb + roffs[0], std::min(sbytes[0], rbytes[0]), s);
+  // a rank knows neither where its block starts in a peer's sbuf nor the
+  // largest pair of the call: the rows travel through the registration page
+  if (!c->reg_shm) return MX_ERR_UNSUPPORTED;   // agreed at creation: every rank returns here
+  const XRow *rows = nullptr;
+  x.mis = (uintptr_t)x.sb & 15;
+  if (int rc = xrow_exchange(c, sbytes, soffs, x.mis | (x.inplace ? 16 : 0), &rows)) return rc;
+  for (int p = 0; p < n; p++) {
+    if (((rows[p].flags >> 4) & 1) != (uint64_t)x.inplace) return MX_ERR_ARG;   // MPI_IN_PLACE on some ranks only: every rank sees it
+    x.send_off[p] = soffs[p];
+    x.send_len[p] = sbytes[p];
+    x.pull_off[p] = (size_t)rows[p].offs[r];
+    x.peer_mis[p] = (size_t)(rows[p].flags & 15);
+    x.recv_off[p] = roffs[p];
+    x.recv_len[p] = std::min((size_t)rows[p].bytes[r], rbytes[p]);   // never past the receiver's size
+    x.sb_span = std::max(x.sb_span, soffs[p] + sbytes[p]);
+    x.rb_span = std::max(x.rb_span, roffs[p] + rbytes[p]);
+    for (int q = 0; q < n; q++) x.max_pair = std::max(x.max_pair, (size_t)rows[p].bytes[q]);
+  }
+  x.zc_bytes = (size_t)n * x.max_pair;
+  if (c->xmin && x.zc_bytes <= c->xmin) return MX_ERR_UNSUPPORTED;   // the same on every rank
+  return exchange_mp(c, x, s);
 }
 
 // MPI_Bcast, all-peer scatter + allgather (the reference's large-message

@@ -160,6 +160,8 @@ struct P2PRndvCur {
 
 }  // namespace mx
 
+namespace mx { struct XTable; }
+
 // a peer allocation mapped for zero-copy collectives.  Key: peer + the
 // exporter's allocation base + its runtime buffer id (HIP_POINTER_ATTRIBUTE_
 // BUFFER_ID): an allocation freed and re-made at the same address -- what a
@@ -256,6 +258,10 @@ struct mx_comm {
   int ev_kind[32];   // 0 fold, 1 push, 2 gather
   double ev_bytes[32];
   mx_coll_stats_t st;
+  uint64_t xst[4];   // exchanges (mx_comm_exchange_stats): calls, zero-copy calls, staged calls, staged rounds
+  size_t xmin;       // alltoallv: calls of size x largest pair <= xmin are declined (mx_comm_set_exchange_min)
+  mx::XTable *xtab;  // table memory of the local forms' n x n launches (mx_exchange.hpp), made on first use
+  uint64_t xrow_seq; // alltoallv row exchanges so far (the registration page's row area)
   // non-blocking / persistent requests: while `defer`
   // is set, finish() leaves the stream running; `tail` is an event after the
   // last deferred collective, which a collective enqueued on another stream

@@ -124,6 +124,12 @@ typedef struct {
     mca_coll_base_module_t *prev_allgather_module;
     mca_coll_base_module_bcast_fn_t prev_bcast;
     mca_coll_base_module_t *prev_bcast_module;
+    mca_coll_base_module_alltoall_fn_t prev_alltoall;
+    mca_coll_base_module_t *prev_alltoall_module;
+    mca_coll_base_module_alltoallv_fn_t prev_alltoallv;
+    mca_coll_base_module_t *prev_alltoallv_module;
+    mca_coll_base_module_allgatherv_fn_t prev_allgatherv;
+    mca_coll_base_module_t *prev_allgatherv_module;
     mca_coll_base_module_reduce_local_fn_t prev_reduce_local;
     mca_coll_base_module_t *prev_reduce_local_module;
     mca_coll_base_module_reduce_fn_t prev_reduce;
@@ -195,6 +201,9 @@ static void coll_module_destruct(mx_coll_module_t *m)
     if (m->prev_reduce_scatter_module) MX_OBJ_RELEASE(m->prev_reduce_scatter_module);
     if (m->prev_allgather_module) MX_OBJ_RELEASE(m->prev_allgather_module);
     if (m->prev_bcast_module) MX_OBJ_RELEASE(m->prev_bcast_module);
+    if (m->prev_alltoall_module) MX_OBJ_RELEASE(m->prev_alltoall_module);
+    if (m->prev_alltoallv_module) MX_OBJ_RELEASE(m->prev_alltoallv_module);
+    if (m->prev_allgatherv_module) MX_OBJ_RELEASE(m->prev_allgatherv_module);
     if (m->prev_reduce_local_module) MX_OBJ_RELEASE(m->prev_reduce_local_module);
     if (m->prev_reduce_module) MX_OBJ_RELEASE(m->prev_reduce_module);
     if (m->prev_reduce_scatter_block_module) MX_OBJ_RELEASE(m->prev_reduce_scatter_block_module);
@@ -240,6 +249,9 @@ static int comm_ready(mx_coll_module_t *m)
          * staged protocol 0 auto / 1 push / 2 pull */
         const int kb = mx_ompi_host->mca_int("coll_mi355x_reg_min_kb", -1);
         (void)mx_comm_set_reg_min(m->mx, kb > 0 ? (size_t)kb << 10 : kb < 0 ? (size_t)256 << 10 : 0);
+        /* alltoallv has no size every rank shares: the library declines the
+         * small ones itself, after its row exchange, on every rank alike */
+        (void)mx_comm_set_exchange_min(m->mx, m->host_max);
         const int proto = mx_ompi_host->mca_int("coll_mi355x_protocol", MX_PROTO_AUTO);
         if (mx_comm_set_protocol(m->mx, proto) < 0) rc = MX_ERR_ARG;
         /* data-movement autotuning of large allreduces (on by default); a
@@ -792,6 +804,155 @@ static int mx_coll_allgather(const void *sbuf, int scount, struct ompi_datatype_
     return host_allgather(m, sbuf, scount, sdtype, rbuf, rcount, rdtype);
 }
 
+/* ---- exchanges: alltoall, alltoallv, allgatherv -----------------------------
+ * Pure data movement: any lower module gives the same bytes, so no forced-
+ * algorithm rule applies.  The device takes a call when the communicator has
+ * at most MX_MAX_RANKS ranks, the call is above coll_mi355x_host_max_kb, both
+ * buffers are device memory and both datatypes are contiguous (counts and
+ * displacements then scale to bytes by the type size); every other call --
+ * host buffers, derived layouts, small calls, MX_ERR_UNSUPPORTED from the
+ * library -- runs on the saved module through host views of the device
+ * buffers.  All of these must hold alike on every rank of a call. */
+static int xch_contig(struct ompi_datatype_t *dt) { return mx_ompi_host->dtype_contiguous(dt, 2); }
+/* sends / recvs: the rank has bytes to send / receive.  A buffer nothing moves
+ * through may be anything (NULL, host memory) and must not change the route,
+ * which every rank has to choose alike. */
+static int xch_device(const void *sbuf, int sends, const void *rbuf, int recvs)
+{
+    return (sbuf == MPI_IN_PLACE || !sends || mx_is_device_ptr(sbuf) == 1) && (!recvs || mx_is_device_ptr(rbuf) == 1);
+}
+static int xch_any(int n, const int *counts)
+{
+    for (int i = 0; i < n; i++)
+        if (counts[i] > 0) return 1;
+    return 0;
+}
+/* elements a v-form's buffer spans: max(displ + count) */
+static size_t xch_span(int n, const int *counts, const int *displs)
+{
+    size_t hi = 0;
+    for (int i = 0; i < n; i++) {
+        const size_t e = (size_t)displs[i] + (size_t)counts[i];
+        if (counts[i] > 0 && e > hi) hi = e;
+    }
+    return hi;
+}
+static void xch_bytes(int n, const int *counts, const int *displs, size_t es, size_t *b, size_t *o)
+{
+    for (int i = 0; i < n; i++) {
+        b[i] = (size_t)counts[i] * es;
+        o[i] = (size_t)displs[i] * es;
+    }
+}
+
+static int host_alltoall(mx_coll_module_t *m, const void *sbuf, int scount, struct ompi_datatype_t *sdtype,
+                         void *rbuf, int rcount, struct ompi_datatype_t *rdtype)
+{
+    const int n = mx_ompi_host->comm_size(m->comm);
+    hview_t s, r;
+    void *hs, *hr;
+    int rc = hview_in(m, SCR_IN, sbuf, sdtype, (size_t)scount * n, 1, &s, &hs);
+    if (!rc) rc = hview_out_in(m, SCR_OUT, rbuf, rdtype, (size_t)rcount * n, sbuf == MPI_IN_PLACE, &r, &hr);
+    if (rc) return map_rc(rc);
+    int ret = m->prev_alltoall(hs, scount, sdtype, hr, rcount, rdtype, m->comm, m->prev_alltoall_module);
+    if (ret == OMPI_SUCCESS) ret = map_rc(hview_out(m, &r));
+    return ret;
+}
+
+static int mx_coll_alltoall(const void *sbuf, int scount, struct ompi_datatype_t *sdtype, void *rbuf, int rcount,
+                            struct ompi_datatype_t *rdtype, struct ompi_communicator_t *comm,
+                            mca_coll_base_module_t *module)
+{
+    mx_coll_module_t *m = (mx_coll_module_t *)module;
+    const size_t rbytes = (size_t)rcount * mx_ompi_host->dtype_size(rdtype);
+    const int n = mx_ompi_host->comm_size(comm), inplace = sbuf == MPI_IN_PLACE;
+    if (rbytes && n <= MX_MAX_RANKS && big(m, rbytes * n) && xch_device(sbuf, 1, rbuf, 1) && xch_contig(rdtype) &&
+        (inplace || xch_contig(sdtype)) && comm_ready(m)) {
+        int rc = begin(m);
+        if (!rc && !inplace && (size_t)scount * mx_ompi_host->dtype_size(sdtype) != rbytes)
+            rc = MX_ERR_ARG;   /* type signatures differ */
+        if (!rc) rc = mx_alltoall(m->mx, inplace ? MX_IN_PLACE : sbuf, rbuf, rbytes, m->stream);
+        if (rc != MX_ERR_UNSUPPORTED) return map_rc(rc);
+    }
+    return host_alltoall(m, sbuf, scount, sdtype, rbuf, rcount, rdtype);
+}
+
+static int host_alltoallv(mx_coll_module_t *m, const void *sbuf, const int *scounts, const int *sdisps,
+                          struct ompi_datatype_t *sdtype, void *rbuf, const int *rcounts, const int *rdisps,
+                          struct ompi_datatype_t *rdtype)
+{
+    const int n = mx_ompi_host->comm_size(m->comm), inplace = sbuf == MPI_IN_PLACE;
+    hview_t s, r;
+    void *hs, *hr;
+    int rc = hview_in(m, SCR_IN, sbuf, sdtype, inplace ? 0 : xch_span(n, scounts, sdisps), 1, &s, &hs);
+    /* the view is copied in: the bytes between the blocks come back unchanged */
+    if (!rc) rc = hview_in(m, SCR_OUT, rbuf, rdtype, xch_span(n, rcounts, rdisps), 1, &r, &hr);
+    if (rc) return map_rc(rc);
+    int ret = m->prev_alltoallv(hs, scounts, sdisps, sdtype, hr, rcounts, rdisps, rdtype, m->comm,
+                                m->prev_alltoallv_module);
+    if (ret == OMPI_SUCCESS) ret = map_rc(hview_out(m, &r));
+    return ret;
+}
+
+static int mx_coll_alltoallv(const void *sbuf, const int *scounts, const int *sdisps, struct ompi_datatype_t *sdtype,
+                             void *rbuf, const int *rcounts, const int *rdisps, struct ompi_datatype_t *rdtype,
+                             struct ompi_communicator_t *comm, mca_coll_base_module_t *module)
+{
+    mx_coll_module_t *m = (mx_coll_module_t *)module;
+    const int n = mx_ompi_host->comm_size(comm), inplace = sbuf == MPI_IN_PLACE;
+    /* no size here is the same on every rank: the library decides on the
+     * call's largest pair after the ranks exchanged their rows (comm_ready) */
+    const int sends = inplace || xch_any(n, scounts), recvs = xch_any(n, rcounts);
+    if (n <= MX_MAX_RANKS && xch_device(sbuf, sends, rbuf, recvs) && xch_contig(rdtype) &&
+        (inplace || xch_contig(sdtype)) && comm_ready(m)) {
+        size_t sb[MX_MAX_RANKS], so[MX_MAX_RANKS], rb[MX_MAX_RANKS], ro[MX_MAX_RANKS];
+        xch_bytes(n, rcounts, rdisps, mx_ompi_host->dtype_size(rdtype), rb, ro);
+        if (!inplace) xch_bytes(n, scounts, sdisps, mx_ompi_host->dtype_size(sdtype), sb, so);
+        int rc = begin(m);
+        if (!rc)
+            rc = mx_alltoallv(m->mx, inplace ? MX_IN_PLACE : sends ? sbuf : NULL, inplace ? NULL : sb,
+                              inplace ? NULL : so, recvs ? rbuf : NULL, rb, ro, m->stream);
+        if (rc != MX_ERR_UNSUPPORTED) return map_rc(rc);
+    }
+    return host_alltoallv(m, sbuf, scounts, sdisps, sdtype, rbuf, rcounts, rdisps, rdtype);
+}
+
+static int host_allgatherv(mx_coll_module_t *m, const void *sbuf, int scount, struct ompi_datatype_t *sdtype,
+                           void *rbuf, const int *rcounts, const int *disps, struct ompi_datatype_t *rdtype)
+{
+    const int n = mx_ompi_host->comm_size(m->comm);
+    hview_t s, r;
+    void *hs, *hr;
+    int rc = hview_in(m, SCR_IN, sbuf, sdtype, (size_t)scount, 1, &s, &hs);
+    if (!rc) rc = hview_in(m, SCR_OUT, rbuf, rdtype, xch_span(n, rcounts, disps), 1, &r, &hr);
+    if (rc) return map_rc(rc);
+    int ret = m->prev_allgatherv(hs, scount, sdtype, hr, rcounts, disps, rdtype, m->comm, m->prev_allgatherv_module);
+    if (ret == OMPI_SUCCESS) ret = map_rc(hview_out(m, &r));
+    return ret;
+}
+
+static int mx_coll_allgatherv(const void *sbuf, int scount, struct ompi_datatype_t *sdtype, void *rbuf,
+                              const int *rcounts, const int *disps, struct ompi_datatype_t *rdtype,
+                              struct ompi_communicator_t *comm, mca_coll_base_module_t *module)
+{
+    mx_coll_module_t *m = (mx_coll_module_t *)module;
+    const int n = mx_ompi_host->comm_size(comm), rank = mx_ompi_host->comm_rank(comm), inplace = sbuf == MPI_IN_PLACE;
+    const size_t es = mx_ompi_host->dtype_size(rdtype);
+    size_t total = 0;   /* (rcounts, rdtype) is significant, and equal, on every rank */
+    for (int i = 0; i < n; i++) total += (size_t)rcounts[i] * es;
+    if (total && n <= MX_MAX_RANKS && big(m, total) && xch_device(sbuf, scount > 0, rbuf, 1) && xch_contig(rdtype) &&
+        (inplace || xch_contig(sdtype)) && comm_ready(m)) {
+        size_t rb[MX_MAX_RANKS], ro[MX_MAX_RANKS];
+        xch_bytes(n, rcounts, disps, es, rb, ro);
+        const size_t sbytes = inplace ? rb[rank] : (size_t)scount * mx_ompi_host->dtype_size(sdtype);
+        int rc = begin(m);
+        if (!rc && sbytes != rb[rank]) rc = MX_ERR_ARG;   /* type signatures differ */
+        if (!rc) rc = mx_allgatherv(m->mx, inplace ? MX_IN_PLACE : sbytes ? sbuf : NULL, sbytes, rbuf, rb, ro, m->stream);
+        if (rc != MX_ERR_UNSUPPORTED) return map_rc(rc);
+    }
+    return host_allgatherv(m, sbuf, scount, sdtype, rbuf, rcounts, disps, rdtype);
+}
+
 static int mx_coll_bcast(void *buf, int count, struct ompi_datatype_t *dtype, int root,
                          struct ompi_communicator_t *comm, mca_coll_base_module_t *module)
 {
@@ -959,6 +1120,54 @@ static int mx_self_allgather(const void *sbuf, int scount, struct ompi_datatype_
     if (!self_device(sbuf, rbuf))
         return m->prev_allgather(sbuf, scount, sdtype, rbuf, rcount, rdtype, comm, m->prev_allgather_module);
     return map_rc(self_copy(m, sbuf, sdtype, (size_t)scount, rbuf, rdtype, (size_t)rcount));
+}
+
+static int mx_self_alltoall(const void *sbuf, int scount, struct ompi_datatype_t *sdtype, void *rbuf, int rcount,
+                            struct ompi_datatype_t *rdtype, struct ompi_communicator_t *comm,
+                            mca_coll_base_module_t *module)
+{
+    mx_coll_module_t *m = (mx_coll_module_t *)module;
+    if (sbuf == MPI_IN_PLACE) return OMPI_SUCCESS;
+    if (!self_device(sbuf, rbuf))
+        return m->prev_alltoall(sbuf, scount, sdtype, rbuf, rcount, rdtype, comm, m->prev_alltoall_module);
+    return map_rc(self_copy(m, sbuf, sdtype, (size_t)scount, rbuf, rdtype, (size_t)rcount));
+}
+
+/* byte offset of `displ` elements of dt: displ x extent, the extent taken
+ * from the host's spans (span(2) - span(1)) */
+static size_t self_displ(struct ompi_datatype_t *dt, int displ)
+{
+    ptrdiff_t lo1 = 0, hi1 = 0, lo2 = 0, hi2 = 0;
+    if (displ <= 0) return 0;
+    if (mx_ompi_host->dtype_span && mx_ompi_host->dtype_span(dt, 1, &lo1, &hi1) == OMPI_SUCCESS &&
+        mx_ompi_host->dtype_span(dt, 2, &lo2, &hi2) == OMPI_SUCCESS)
+        return (size_t)displ * (size_t)((hi2 - lo2) - (hi1 - lo1));
+    return (size_t)displ * mx_ompi_host->dtype_size(dt);
+}
+
+static int mx_self_alltoallv(const void *sbuf, const int *scounts, const int *sdisps, struct ompi_datatype_t *sdtype,
+                             void *rbuf, const int *rcounts, const int *rdisps, struct ompi_datatype_t *rdtype,
+                             struct ompi_communicator_t *comm, mca_coll_base_module_t *module)
+{
+    mx_coll_module_t *m = (mx_coll_module_t *)module;
+    if (sbuf == MPI_IN_PLACE) return OMPI_SUCCESS;
+    if (!self_device(sbuf, rbuf))
+        return m->prev_alltoallv(sbuf, scounts, sdisps, sdtype, rbuf, rcounts, rdisps, rdtype, comm,
+                                 m->prev_alltoallv_module);
+    return map_rc(self_copy(m, (const char *)sbuf + self_displ(sdtype, sdisps[0]), sdtype, (size_t)scounts[0],
+                            (char *)rbuf + self_displ(rdtype, rdisps[0]), rdtype, (size_t)rcounts[0]));
+}
+
+static int mx_self_allgatherv(const void *sbuf, int scount, struct ompi_datatype_t *sdtype, void *rbuf,
+                              const int *rcounts, const int *disps, struct ompi_datatype_t *rdtype,
+                              struct ompi_communicator_t *comm, mca_coll_base_module_t *module)
+{
+    mx_coll_module_t *m = (mx_coll_module_t *)module;
+    if (sbuf == MPI_IN_PLACE) return OMPI_SUCCESS;
+    if (!self_device(sbuf, rbuf))
+        return m->prev_allgatherv(sbuf, scount, sdtype, rbuf, rcounts, disps, rdtype, comm, m->prev_allgatherv_module);
+    return map_rc(self_copy(m, sbuf, sdtype, (size_t)scount, (char *)rbuf + self_displ(rdtype, disps[0]), rdtype,
+                            (size_t)rcounts[0]));
 }
 
 static int mx_self_reduce(const void *sbuf, void *rbuf, int count, struct ompi_datatype_t *dtype, struct ompi_op_t *op,
@@ -1839,6 +2048,7 @@ static int mx_coll_module_enable(mca_coll_base_module_t *module, struct ompi_com
     }
         SAVE_PREV_SELF(allreduce) SAVE_PREV_SELF(reduce_scatter) SAVE_PREV_SELF(allgather) SAVE_PREV_SELF(reduce)
         SAVE_PREV_SELF(reduce_scatter_block) SAVE_PREV_SELF(scan)
+        SAVE_PREV_SELF(alltoall) SAVE_PREV_SELF(alltoallv) SAVE_PREV_SELF(allgatherv)
 #undef SAVE_PREV_SELF
         if (m->super.coll_reduce_local) SAVE_PREV(m, comm, reduce_local, mca_coll_base_module_reduce_local_fn_t);
         m->mx_state = -1;   /* no peers: no device communicator */
@@ -1853,6 +2063,9 @@ static int mx_coll_module_enable(mca_coll_base_module_t *module, struct ompi_com
         SAVE_PREV(m, comm, reduce_scatter_block, mca_coll_base_module_reduce_scatter_block_fn_t);
         SAVE_PREV(m, comm, scan, mca_coll_base_module_scan_fn_t);
         SAVE_PREV(m, comm, exscan, mca_coll_base_module_exscan_fn_t);
+        SAVE_PREV(m, comm, alltoall, mca_coll_base_module_alltoall_fn_t);
+        SAVE_PREV(m, comm, alltoallv, mca_coll_base_module_alltoallv_fn_t);
+        SAVE_PREV(m, comm, allgatherv, mca_coll_base_module_allgatherv_fn_t);
     }
     if (m->super.coll_reduce_local) SAVE_PREV(m, comm, reduce_local, mca_coll_base_module_reduce_local_fn_t);
     /* nonblocking / persistent: take a slot only where a lower module
@@ -1926,6 +2139,9 @@ static mca_coll_base_module_t *mx_coll_component_comm_query(struct ompi_communic
         m->super.coll_reduce_scatter_block = mx_coll_reduce_scatter_block;
         m->super.coll_scan = mx_coll_scan;
         m->super.coll_exscan = mx_coll_exscan;
+        m->super.coll_alltoall = mx_coll_alltoall;
+        m->super.coll_alltoallv = mx_coll_alltoallv;
+        m->super.coll_allgatherv = mx_coll_allgatherv;
 #define SET_NB(name) m->super.coll_##name = mx_coll_##name;
         MX_NB_SLOTS(SET_NB)
 #undef SET_NB
@@ -1940,6 +2156,9 @@ static mca_coll_base_module_t *mx_coll_component_comm_query(struct ompi_communic
         m->super.coll_reduce_scatter_block = mx_self_reduce_scatter_block;
         m->super.coll_scan = mx_self_scan;
         m->super.coll_exscan = mx_self_exscan;
+        m->super.coll_alltoall = mx_self_alltoall;
+        m->super.coll_alltoallv = mx_self_alltoallv;
+        m->super.coll_allgatherv = mx_self_allgatherv;
     }
     if (*priority > 75) m->super.coll_reduce_local = mx_coll_reduce_local;
     return &m->super;

@@ -352,16 +352,18 @@ static int mca_int(const char *name, int def)
 }
 
 /* ---- communicators --------------------------------------------------------- */
-#define NSLOTS 25
+#define NSLOTS 28
 static const char *g_slot_names[NSLOTS] = {
     "allreduce", "reduce_scatter", "allgather", "bcast", "reduce_local", "reduce", "reduce_scatter_block", "scan",
     "exscan",
     /* nonblocking (coll.h:534-550) and persistent (:553-569) */
     "iallreduce", "ireduce", "ireduce_scatter", "ireduce_scatter_block", "iscan", "iexscan", "iallgather", "ibcast",
     "allreduce_init", "reduce_init", "reduce_scatter_init", "reduce_scatter_block_init", "scan_init", "exscan_init",
-    "allgather_init", "bcast_init"};
+    "allgather_init", "bcast_init",
+    /* exchanges (coll.h:204-219), appended: the indices above stay */
+    "alltoall", "alltoallv", "allgatherv"};
 enum { S_IALLREDUCE = 9, S_IREDUCE, S_IREDUCE_SCATTER, S_IREDUCE_SCATTER_BLOCK, S_ISCAN, S_IEXSCAN, S_IALLGATHER,
-       S_IBCAST, S_PERSISTENT0 };
+       S_IBCAST, S_PERSISTENT0, S_ALLTOALL = 25, S_ALLTOALLV, S_ALLGATHERV };
 
 struct ompi_communicator_t {
     int rank, size;
@@ -819,6 +821,94 @@ static int base_bcast(void *buf, int count, struct ompi_datatype_t *dt, int root
     return OMPI_SUCCESS;
 }
 
+/* exchanges on gather(): every rank contributes its packed send row, padded
+ * to the longest, and takes its blocks out of the others' rows */
+static int base_alltoall(const void *sbuf, int scount, struct ompi_datatype_t *sdt, void *rbuf, int rcount,
+                         struct ompi_datatype_t *rdt, struct ompi_communicator_t *c, mca_coll_base_module_t *m)
+{
+    (void)m;
+    const int n = c->size;
+    const size_t blk = (size_t)rcount * rdt->size, rext = (size_t)rcount * dtype_extent(rdt);
+    char *mine = calloc(1, blk * n + 1), *all;
+    if (!mine) return OMPI_ERR_OUT_OF_RESOURCE;
+    for (int p = 0; p < n; p++) {
+        if (sbuf == MPI_IN_PLACE) dtype_pack(rdt, rcount, (char *)rbuf + p * rext, mine + p * blk);
+        else dtype_pack(sdt, scount, (const char *)sbuf + (size_t)p * scount * dtype_extent(sdt), mine + p * blk);
+    }
+    all = gather(c, mine, blk * n);
+    free(mine);
+    if (!all) return OMPI_ERROR;
+    for (int p = 0; p < n; p++)
+        dtype_unpack(rdt, rcount, all + ((size_t)p * n + c->rank) * blk, (char *)rbuf + p * rext);
+    free(all);
+    return OMPI_SUCCESS;
+}
+
+static int base_alltoallv(const void *sbuf, const int *scounts, const int *sdisps, struct ompi_datatype_t *sdt,
+                          void *rbuf, const int *rcounts, const int *rdisps, struct ompi_datatype_t *rdt,
+                          struct ompi_communicator_t *c, mca_coll_base_module_t *m)
+{
+    (void)m;
+    const int n = c->size, inplace = sbuf == MPI_IN_PLACE;
+    if (inplace) { sbuf = rbuf; scounts = rcounts; sdisps = rdisps; sdt = rdt; }
+    /* the byte sizes of every rank's row, then the rows */
+    size_t *row = calloc((size_t)n, sizeof *row), *B, maxrow = 0;
+    if (!row) return OMPI_ERR_OUT_OF_RESOURCE;
+    for (int q = 0; q < n; q++) row[q] = (size_t)scounts[q] * sdt->size;
+    B = (size_t *)gather(c, row, (size_t)n * sizeof *row);
+    free(row);
+    if (!B) return OMPI_ERROR;
+    for (int p = 0; p < n; p++) {
+        size_t t = 0;
+        for (int q = 0; q < n; q++) t += B[(size_t)p * n + q];
+        if (t > maxrow) maxrow = t;
+    }
+    char *mine = calloc(1, maxrow + 1), *all;
+    if (!mine) { free(B); return OMPI_ERR_OUT_OF_RESOURCE; }
+    size_t o = 0;
+    for (int q = 0; q < n; q++) {
+        dtype_pack(sdt, scounts[q], (const char *)sbuf + (size_t)sdisps[q] * dtype_extent(sdt), mine + o);
+        o += (size_t)scounts[q] * sdt->size;
+    }
+    all = gather(c, mine, maxrow);
+    free(mine);
+    if (!all) { free(B); return OMPI_ERROR; }
+    for (int p = 0; p < n; p++) {
+        size_t off = 0, len = B[(size_t)p * n + c->rank];
+        for (int q = 0; q < c->rank; q++) off += B[(size_t)p * n + q];
+        if (len > (size_t)rcounts[p] * rdt->size) len = (size_t)rcounts[p] * rdt->size;   /* never past the receive count */
+        dtype_unpack(rdt, (int)(len / rdt->size), all + (size_t)p * maxrow + off,
+                     (char *)rbuf + (size_t)rdisps[p] * dtype_extent(rdt));
+    }
+    free(all);
+    free(B);
+    return OMPI_SUCCESS;
+}
+
+static int base_allgatherv(const void *sbuf, int scount, struct ompi_datatype_t *sdt, void *rbuf, const int *rcounts,
+                           const int *disps, struct ompi_datatype_t *rdt, struct ompi_communicator_t *c,
+                           mca_coll_base_module_t *m)
+{
+    (void)m;
+    const int n = c->size;
+    size_t maxb = 0;
+    for (int p = 0; p < n; p++)
+        if ((size_t)rcounts[p] * rdt->size > maxb) maxb = (size_t)rcounts[p] * rdt->size;
+    char *mine = calloc(1, maxb + 1), *all;
+    if (!mine) return OMPI_ERR_OUT_OF_RESOURCE;
+    if (sbuf == MPI_IN_PLACE)
+        dtype_pack(rdt, rcounts[c->rank], (char *)rbuf + (size_t)disps[c->rank] * dtype_extent(rdt), mine);
+    else
+        dtype_pack(sdt, scount, sbuf, mine);
+    all = gather(c, mine, maxb);
+    free(mine);
+    if (!all) return OMPI_ERROR;
+    for (int p = 0; p < n; p++)
+        dtype_unpack(rdt, rcounts[p], all + (size_t)p * maxb, (char *)rbuf + (size_t)disps[p] * dtype_extent(rdt));
+    free(all);
+    return OMPI_SUCCESS;
+}
+
 /* coll/self-like reduce_local: mca_coll_base_reduce_local (coll_base_reduce.c:42-49) */
 static int base_reduce_local(const void *in, void *inout, int count, struct ompi_datatype_t *dt, struct ompi_op_t *op,
                              mca_coll_base_module_t *m)
@@ -874,6 +964,28 @@ static int self_allgather(const void *sbuf, int scount, struct ompi_datatype_t *
 {
     (void)c; (void)m;
     return self_copy(sbuf, sdt, scount, rbuf, rdt, rcount);
+}
+static int self_alltoall(const void *sbuf, int scount, struct ompi_datatype_t *sdt, void *rbuf, int rcount,
+                         struct ompi_datatype_t *rdt, struct ompi_communicator_t *c, mca_coll_base_module_t *m)
+{
+    (void)c; (void)m;
+    return self_copy(sbuf, sdt, scount, rbuf, rdt, rcount);
+}
+static int self_alltoallv(const void *sbuf, const int *scounts, const int *sdisps, struct ompi_datatype_t *sdt,
+                          void *rbuf, const int *rcounts, const int *rdisps, struct ompi_datatype_t *rdt,
+                          struct ompi_communicator_t *c, mca_coll_base_module_t *m)
+{
+    (void)c; (void)m;
+    if (sbuf == MPI_IN_PLACE) return self_copy(sbuf, rdt, 0, rbuf, rdt, 0);
+    return self_copy((const char *)sbuf + (size_t)sdisps[0] * dtype_extent(sdt), sdt, scounts[0],
+                     (char *)rbuf + (size_t)rdisps[0] * dtype_extent(rdt), rdt, rcounts[0]);
+}
+static int self_allgatherv(const void *sbuf, int scount, struct ompi_datatype_t *sdt, void *rbuf, const int *rcounts,
+                           const int *disps, struct ompi_datatype_t *rdt, struct ompi_communicator_t *c,
+                           mca_coll_base_module_t *m)
+{
+    (void)c; (void)m;
+    return self_copy(sbuf, sdt, scount, (char *)rbuf + (size_t)disps[0] * dtype_extent(rdt), rdt, rcounts[0]);
 }
 static int self_bcast(void *buf, int count, struct ompi_datatype_t *dt, int root, struct ompi_communicator_t *c,
                       mca_coll_base_module_t *m)
@@ -1312,7 +1424,9 @@ static int comm_select(struct ompi_communicator_t *c, int is_self)
                             (void *)(MOD)->coll_reduce_init, (void *)(MOD)->coll_reduce_scatter_init, \
                             (void *)(MOD)->coll_reduce_scatter_block_init,                           \
                             (void *)(MOD)->coll_scan_init, (void *)(MOD)->coll_exscan_init,          \
-                            (void *)(MOD)->coll_allgather_init, (void *)(MOD)->coll_bcast_init};     \
+                            (void *)(MOD)->coll_allgather_init, (void *)(MOD)->coll_bcast_init,      \
+                            (void *)(MOD)->coll_alltoall, (void *)(MOD)->coll_alltoallv,             \
+                            (void *)(MOD)->coll_allgatherv};                                         \
         for (int i_ = 0; i_ < NSLOTS; i_++)                                                          \
             if (f_[i_]) { c->fn[i_] = f_[i_]; c->mod[i_] = (MOD); c->owner[i_] = (OWNER); }          \
     } while (0)
@@ -1329,6 +1443,9 @@ static int comm_select(struct ompi_communicator_t *c, int is_self)
         b->coll_reduce_scatter_block = self_reduce_scatter_block;
         b->coll_scan = self_scan;
         b->coll_exscan = self_exscan;
+        b->coll_alltoall = self_alltoall;
+        b->coll_alltoallv = self_alltoallv;
+        b->coll_allgatherv = self_allgatherv;
         COPY(b, "self");
         base_prio = 75;
     } else {
@@ -1345,6 +1462,9 @@ static int comm_select(struct ompi_communicator_t *c, int is_self)
         b->coll_reduce_scatter_block = basic_reduce_scatter_block;
         b->coll_scan = basic_scan;
         b->coll_exscan = basic_exscan;
+        b->coll_alltoall = base_alltoall;
+        b->coll_alltoallv = base_alltoallv;
+        b->coll_allgatherv = base_allgatherv;
         if (!coll_excluded("basic")) COPY(b, "basic");
         /* libnbc (10): the nonblocking and persistent slots */
         b = &g_libnbc_coll;
@@ -1369,6 +1489,10 @@ static int comm_select(struct ompi_communicator_t *c, int is_self)
         b->coll_bcast = base_bcast;
         b->coll_reduce = tuned_reduce;
         b->coll_reduce_scatter_block = tuned_reduce_scatter_block;
+        /* coll_tuned_decision_fixed.c:97, :177, :640: data movement, any algorithm */
+        b->coll_alltoall = base_alltoall;
+        b->coll_alltoallv = base_alltoallv;
+        b->coll_allgatherv = base_allgatherv;
         {
             int fan;
             if (tuned_forced("scan", &fan)) b->coll_scan = tuned_scan;
@@ -1579,6 +1703,29 @@ int mxh_allgather(const void *sbuf, int scount, void *sdt, void *rbuf, int rcoun
 {
     struct ompi_communicator_t *c = cv;
     return ((mca_coll_base_module_allgather_fn_t)c->fn[2])(sbuf, scount, sdt, rbuf, rcount, rdt, c, c->mod[2]);
+}
+
+int mxh_alltoall(const void *sbuf, int scount, void *sdt, void *rbuf, int rcount, void *rdt, void *cv)
+{
+    struct ompi_communicator_t *c = cv;
+    return ((mca_coll_base_module_alltoall_fn_t)c->fn[S_ALLTOALL])(sbuf, scount, sdt, rbuf, rcount, rdt, c,
+                                                                   c->mod[S_ALLTOALL]);
+}
+
+int mxh_alltoallv(const void *sbuf, const int *scounts, const int *sdisps, void *sdt, void *rbuf,
+                  const int *rcounts, const int *rdisps, void *rdt, void *cv)
+{
+    struct ompi_communicator_t *c = cv;
+    return ((mca_coll_base_module_alltoallv_fn_t)c->fn[S_ALLTOALLV])(sbuf, scounts, sdisps, sdt, rbuf, rcounts, rdisps,
+                                                                     rdt, c, c->mod[S_ALLTOALLV]);
+}
+
+int mxh_allgatherv(const void *sbuf, int scount, void *sdt, void *rbuf, const int *rcounts, const int *disps,
+                   void *rdt, void *cv)
+{
+    struct ompi_communicator_t *c = cv;
+    return ((mca_coll_base_module_allgatherv_fn_t)c->fn[S_ALLGATHERV])(sbuf, scount, sdt, rbuf, rcounts, disps, rdt, c,
+                                                                       c->mod[S_ALLGATHERV]);
 }
 
 int mxh_bcast(void *buf, int count, void *dt, int root, void *cv)

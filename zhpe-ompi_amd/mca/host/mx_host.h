@@ -99,6 +99,13 @@ int mxh_reduce_local(const void *in, void *inout, int count, void *dtype, void *
 int mxh_allreduce(const void *sbuf, void *rbuf, int count, void *dtype, void *op, void *comm);
 int mxh_reduce_scatter(const void *sbuf, void *rbuf, const int *rcounts, void *dtype, void *op, void *comm);
 int mxh_allgather(const void *sbuf, int scount, void *sdtype, void *rbuf, int rcount, void *rdtype, void *comm);
+/* MPI_Alltoall / MPI_Alltoallv / MPI_Allgatherv: counts and displacements in
+ * elements (displacements in extents) of the datatypes */
+int mxh_alltoall(const void *sbuf, int scount, void *sdtype, void *rbuf, int rcount, void *rdtype, void *comm);
+int mxh_alltoallv(const void *sbuf, const int *scounts, const int *sdispls, void *sdtype, void *rbuf,
+                  const int *rcounts, const int *rdispls, void *rdtype, void *comm);
+int mxh_allgatherv(const void *sbuf, int scount, void *sdtype, void *rbuf, const int *rcounts, const int *displs,
+                   void *rdtype, void *comm);
 int mxh_bcast(void *buf, int count, void *dtype, int root, void *comm);
 int mxh_reduce(const void *sbuf, void *rbuf, int count, void *dtype, void *op, int root, void *comm);
 int mxh_reduce_scatter_block(const void *sbuf, void *rbuf, int rcount, void *dtype, void *op, void *comm);

@@ -173,8 +173,17 @@ typedef int (*mca_coll_base_module_disable_1_2_0_fn_t)(mca_coll_base_module_t *m
 typedef int (*mca_coll_base_module_allgather_fn_t)(const void *sbuf, int scount, struct ompi_datatype_t *sdtype,
                                                    void *rbuf, int rcount, struct ompi_datatype_t *rdtype,
                                                    struct ompi_communicator_t *comm, mca_coll_base_module_t *module);
+typedef int (*mca_coll_base_module_allgatherv_fn_t)(const void *sbuf, int scount, struct ompi_datatype_t *sdtype,
+                                                    void *rbuf, const int *rcounts, const int *disps,
+                                                    struct ompi_datatype_t *rdtype, struct ompi_communicator_t *comm,
+                                                    mca_coll_base_module_t *module);
 typedef int (*mca_coll_base_module_allreduce_fn_t)(const void *sbuf, void *rbuf, int count,
                                                    struct ompi_datatype_t *dtype, struct ompi_op_t *op,
+                                                   struct ompi_communicator_t *comm, mca_coll_base_module_t *module);
+typedef mca_coll_base_module_allgather_fn_t mca_coll_base_module_alltoall_fn_t;   /* the same argument list */
+typedef int (*mca_coll_base_module_alltoallv_fn_t)(const void *sbuf, const int *scounts, const int *sdisps,
+                                                   struct ompi_datatype_t *sdtype, void *rbuf, const int *rcounts,
+                                                   const int *rdisps, struct ompi_datatype_t *rdtype,
                                                    struct ompi_communicator_t *comm, mca_coll_base_module_t *module);
 typedef int (*mca_coll_base_module_bcast_fn_t)(void *buff, int count, struct ompi_datatype_t *datatype, int root,
                                                struct ompi_communicator_t *comm, mca_coll_base_module_t *module);
@@ -247,9 +256,11 @@ struct mca_coll_base_module_2_3_0_t {
     mca_coll_base_module_enable_1_1_0_fn_t coll_module_enable;
     /* blocking */
     mca_coll_base_module_allgather_fn_t coll_allgather;
-    mx_coll_slot_unused_t coll_allgatherv;
+    mca_coll_base_module_allgatherv_fn_t coll_allgatherv;
     mca_coll_base_module_allreduce_fn_t coll_allreduce;
-    mx_coll_slot_unused_t coll_alltoall, coll_alltoallv, coll_alltoallw, coll_barrier;
+    mca_coll_base_module_alltoall_fn_t coll_alltoall;
+    mca_coll_base_module_alltoallv_fn_t coll_alltoallv;
+    mx_coll_slot_unused_t coll_alltoallw, coll_barrier;
     mca_coll_base_module_bcast_fn_t coll_bcast;
     mca_coll_base_module_exscan_fn_t coll_exscan;
     mx_coll_slot_unused_t coll_gather, coll_gatherv;

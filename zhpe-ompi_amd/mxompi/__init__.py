@@ -304,6 +304,17 @@ def _coll_lib():
         L.mx_allgather.argtypes = [vp, vp, vp, sz, vp]
         L.mx_allgather_local.argtypes = [vp, pp, pp, sz, vp]
         L.mx_bcast.argtypes = [vp, vp, sz, i, vp]
+        szp = ctypes.POINTER(sz)
+        L.mx_alltoall.argtypes = [vp, vp, vp, sz, vp]
+        L.mx_alltoallv.argtypes = [vp, vp, szp, szp, vp, szp, szp, vp]
+        L.mx_allgatherv.argtypes = [vp, vp, sz, vp, szp, szp, vp]
+        L.mx_alltoall_local.argtypes = [vp, pp, pp, sz, vp]
+        L.mx_alltoallv_local.argtypes = [vp, pp, szp, szp, pp, szp, szp, vp]
+        L.mx_allgatherv_local.argtypes = [vp, pp, pp, szp, szp, vp]
+        L.mx_comm_exchange_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
+        L.mx_exchange_geometry.argtypes = [szp, szp]
+        L.mx_comm_exchange_rounds.argtypes = [vp, sz]
+        L.mx_comm_exchange_rounds.restype = ctypes.c_longlong
         L.mx_bcast_local.argtypes = [vp, pp, sz, i, vp]
         L.mx_allreduce_decision.argtypes = [i, sz, i]
         L.mx_comm_set_profiling.argtypes = [vp, i]
@@ -360,6 +371,8 @@ def _coll_lib():
 
 
 def _ptrs(seq):
+    if isinstance(seq, ctypes.Array):
+        return seq
     arr = (ctypes.c_void_p * len(seq))()
     for k, p in enumerate(seq):
         arr[k] = p
@@ -465,6 +478,35 @@ def iallreduce_decision(n, count, t, inplace=False):
 
 def ireduce_decision(n, count, t):
     return _coll_lib().mx_ireduce_decision(n, count, _slot(t))
+
+
+def _sizes(v):
+    """A size_t array from a sequence (None stays NULL; an array made by an
+    earlier call passes through, for callers that repeat a call)."""
+    if v is None or isinstance(v, ctypes.Array):
+        return v
+    v = [int(x) for x in v]
+    return (ctypes.c_size_t * len(v))(*v)
+
+
+def exchange_geometry():
+    """(bytes one workgroup moves, bytes one wave step moves) in the exchange kernel."""
+    b, w = ctypes.c_size_t(), ctypes.c_size_t()
+    check(_coll_lib().mx_exchange_geometry(ctypes.byref(b), ctypes.byref(w)), "mx_exchange_geometry")
+    return b.value, w.value
+
+
+def exchange_tables_live():
+    """Table memories of the exchange kernel alive in this process (a test hook)."""
+    return _coll_lib().mx_exchange_tables_live()
+
+
+def exchange_stats_total():
+    """Exchange calls of every communicator of this process (mx_comm_exchange_stats
+    with a null communicator): what a caller above the coll component can see."""
+    out = (ctypes.c_uint64 * 4)()
+    check(_coll_lib().mx_comm_exchange_stats(None, out), "mx_comm_exchange_stats")
+    return dict(zip(("calls", "zero_copy_calls", "staged_calls", "staged_rounds"), (int(v) for v in out)))
 
 
 class Comm:
@@ -589,6 +631,32 @@ class Comm:
     def allgather(self, sbuf, rbuf, nbytes, stream=0):
         check(_coll_lib().mx_allgather(self.h, sbuf, rbuf, nbytes, stream or None), "mx_allgather")
 
+    # exchanges: sizes in bytes, displacements byte offsets, one entry per
+    # rank; sbuf None = MPI_IN_PLACE
+    def alltoall(self, sbuf, rbuf, nbytes, stream=0):
+        check(_coll_lib().mx_alltoall(self.h, sbuf, rbuf, nbytes, stream or None), "mx_alltoall")
+
+    def alltoallv(self, sbuf, sbytes, soffs, rbuf, rbytes, roffs, stream=0):
+        check(_coll_lib().mx_alltoallv(self.h, sbuf, _sizes(sbytes), _sizes(soffs), rbuf, _sizes(rbytes),
+                                       _sizes(roffs), stream or None), "mx_alltoallv")
+
+    def allgatherv(self, sbuf, sbytes, rbuf, rbytes, roffs, stream=0):
+        check(_coll_lib().mx_allgatherv(self.h, sbuf, sbytes, rbuf, _sizes(rbytes), _sizes(roffs),
+                                        stream or None), "mx_allgatherv")
+
+    def exchange_stats(self):
+        """Exchange calls of this communicator (mx_comm_exchange_stats): all,
+        zero-copy, staged, and the staging rounds the staged ones took."""
+        out = (ctypes.c_uint64 * 4)()
+        check(_coll_lib().mx_comm_exchange_stats(self.h, out), "mx_comm_exchange_stats")
+        return dict(zip(("calls", "zero_copy_calls", "staged_calls", "staged_rounds"), (int(v) for v in out)))
+
+    def exchange_rounds(self, max_pair):
+        """Staging rounds of a staged exchange whose largest pair is max_pair bytes."""
+        rc = _coll_lib().mx_comm_exchange_rounds(self.h, max_pair)
+        check(min(rc, 0), "mx_comm_exchange_rounds")
+        return rc
+
     def shmem_reduce(self, op, t, dt_size, target, source, nreduce, stream=0):
         """shmem_<t>_<op>_to_all over this communicator's ranks (scoll/mpi path)."""
         sops = ["AND", "OR", "XOR", "MAX", "MIN", "SUM", "PROD"]
@@ -706,6 +774,22 @@ class Comm:
         sp = _ptrs(sbufs) if sbufs is not None else None
         check(_coll_lib().mx_allgather_local(self.h, sp, _ptrs(rbufs), nbytes, stream or None),
               "mx_allgather_local")
+
+    def alltoall_local(self, sbufs, rbufs, nbytes, stream=0):
+        sp = _ptrs(sbufs) if sbufs is not None else None
+        check(_coll_lib().mx_alltoall_local(self.h, sp, _ptrs(rbufs), nbytes, stream or None), "mx_alltoall_local")
+
+    def alltoallv_local(self, sbufs, sbytes, soffs, rbufs, rbytes, roffs, stream=0):
+        """The size x size matrices (row-major, row = the rank owning the
+        buffer) as flat sequences; sbufs None = in place on every rank."""
+        sp = _ptrs(sbufs) if sbufs is not None else None
+        check(_coll_lib().mx_alltoallv_local(self.h, sp, _sizes(sbytes), _sizes(soffs), _ptrs(rbufs),
+                                             _sizes(rbytes), _sizes(roffs), stream or None), "mx_alltoallv_local")
+
+    def allgatherv_local(self, sbufs, rbufs, rbytes, roffs, stream=0):
+        sp = _ptrs(sbufs) if sbufs is not None else None
+        check(_coll_lib().mx_allgatherv_local(self.h, sp, _ptrs(rbufs), _sizes(rbytes), _sizes(roffs),
+                                              stream or None), "mx_allgatherv_local")
 
     def bcast_local(self, bufs, nbytes, root, stream=0):
         check(_coll_lib().mx_bcast_local(self.h, _ptrs(bufs), nbytes, root, stream or None), "mx_bcast_local")
