@@ -51,6 +51,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "mx_convertor.h"
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -346,6 +348,47 @@ int mx_comm_exchange_stats(mx_comm_t *comm, uint64_t out[4]);
  * small calls and no size of its own that all ranks share.  0 = never. */
 int mx_comm_set_exchange_min(mx_comm_t *comm, size_t min_bytes);
 
+/* Exchanges of strided datatypes (transposes, pencil redistributions, halo
+ * columns): one fused kernel reads the sender's layout and writes the
+ * receiver's (csrc/mx_exchange_vec.hip), with no packed buffer in between.
+ * Counts are instances and displacements multiples of the datatype's extent,
+ * as in MPI; a NULL datatype means bytes.  sbuf MX_IN_PLACE follows the byte
+ * forms: the receive description serves both sides.  A receiver with less
+ * room than its sender announces takes only its own stream bytes.  Size 1 is
+ * one job on the caller's stream.
+ *
+ * A datatype qualifies (mx_ddt_strided: 1 or 0) when it flattens to ONE run
+ * of one level -- MPI_Type_vector, hvector, resized contiguous types --, its
+ * blocks are at most 4 MiB and, on the receiving side, its layout is
+ * monotonic.  The word a job moves by is the largest power of two up to 16
+ * that divides block length, displacement, stride, extent and address of
+ * both sides; it must be at least 4 (2-byte blocks are not taken).
+ *
+ * Both forms begin with one row exchange through the registration page, in
+ * which every rank publishes its send layout, its units, its counts and
+ * displacements, its in-place bit and a verdict.  A rank that cannot
+ * describe its datatype passes MX_DDT_NONE and still takes part.  When any
+ * rank refuses, a datatype does not qualify, a word would be below 4 bytes,
+ * the call is at or under mx_comm_set_exchange_min or the communicator has
+ * no registration page, every rank returns MX_ERR_UNSUPPORTED before any
+ * byte moves; the communicator stays usable.  Two-level and multi-run
+ * layouts, indexed types and allgatherv are not taken.
+ * Data path: from mx_comm_set_reg_min bytes up and not in place, every rank
+ * pulls its blocks from the peers' registered send spans straight into its
+ * receive layout (both sides strided); otherwise the blocks go through the
+ * staging in rounds, strided -> flat slot and flat slot -> strided. */
+#define MX_DDT_NONE ((const mx_ddt_t *)1)
+int mx_ddt_strided(const mx_ddt_t *ddt, int receive_side);
+int mx_alltoall_ddt(mx_comm_t *comm, const void *sbuf, size_t scount, const mx_ddt_t *sddt, void *rbuf,
+                    size_t rcount, const mx_ddt_t *rddt, void *stream);
+int mx_alltoallv_ddt(mx_comm_t *comm, const void *sbuf, const size_t *scounts, const int64_t *sdispls,
+                     const mx_ddt_t *sddt, void *rbuf, const size_t *rcounts, const int64_t *rdispls,
+                     const mx_ddt_t *rddt, void *stream);
+/* out: [0] calls of the two above and their _local forms, [1] zero-copy
+ * calls, [2] staged calls, [3] staged rounds (mx_comm_exchange_stats does not
+ * count them).  comm NULL: the sums over this process's communicators. */
+int mx_comm_exchange_ddt_stats(mx_comm_t *comm, uint64_t out[4]);
+
 /* Rooted reduce (coll slot `reduce`, coll.h:239-241): the result lands in
  * rbuf on `root` only (rbuf may be NULL elsewhere); sbuf MPI_IN_PLACE on
  * the root.  Bit-identical to the reference algorithm `alg` (the tree of
@@ -600,6 +643,15 @@ int mx_alltoallv_local(mx_comm_t *comm, const void *const *sbufs, const size_t *
                        void *const *rbufs, const size_t *rbytes, const size_t *roffs, void *stream);
 int mx_allgatherv_local(mx_comm_t *comm, const void *const *sbufs, void *const *rbufs, const size_t *rbytes,
                         const size_t *roffs, void *stream);
+/* The strided forms (mx_alltoallv_ddt) on a local communicator, one launch
+ * per MX_MAX_RANKS jobs: every rank uses sddt / rddt; the size x size
+ * matrices hold instances and displacements in extents, laid out as
+ * mx_alltoallv_local's.  MX_ERR_UNSUPPORTED leaves every buffer untouched. */
+int mx_alltoall_ddt_local(mx_comm_t *comm, const void *const *sbufs, size_t scount, const mx_ddt_t *sddt,
+                          void *const *rbufs, size_t rcount, const mx_ddt_t *rddt, void *stream);
+int mx_alltoallv_ddt_local(mx_comm_t *comm, const void *const *sbufs, const size_t *scounts, const int64_t *sdispls,
+                           const mx_ddt_t *sddt, void *const *rbufs, const size_t *rcounts, const int64_t *rdispls,
+                           const mx_ddt_t *rddt, void *stream);
 int mx_reduce_local(mx_comm_t *comm, const void *const *sbufs, void *const *rbufs, size_t count,
                     int type, int op, int root, int alg, void *stream);
 int mx_scan_local(mx_comm_t *comm, const void *const *sbufs, void *const *rbufs, size_t count,

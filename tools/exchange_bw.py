@@ -15,6 +15,16 @@ read + write traffic (2 x payload) over call time; the share is of the
 6.29 TB/s float4 copy rate measured for this part.
 
     python tools/exchange_bw.py [--out profiles/r07/exchange_local.txt]
+
+--ddt times the strided exchange instead (profiles/r08/exchange_ddt_local.txt):
+per shape and pair size, on the same bytes,
+  (f) alltoall_ddt_local: the fused kernel, sender's layout to receiver's
+  (p) Datatype.pack on every rank -> alltoall_local -> Datatype.unpack on
+      every rank: the three-launch composition through packed buffers
+  (k) allgather_local of the packed bytes: k_copy, the yardstick
+Shapes: 16-byte words (blen 64 / stride 128 on both sides), 8-byte words
+(blen 8 / stride 16 on both sides), and a 4-byte element transpose (blen 4 /
+stride 8 sent, flat received).  GB/s counts the payload read and written once.
 """
 import argparse
 import os
@@ -47,10 +57,90 @@ def _time(fn, payload):
     return t, 2 * payload / t / 1e9
 
 
+def _vector(es, count, blocklen, stride_bytes):
+    """mxompi.Datatype of `count` blocks of `blocklen` elements of `es` bytes
+    every stride_bytes; the extent continues the period."""
+    import struct
+    import mxompi
+    size = count * blocklen * es
+    desc = struct.pack("<HHIQqq", 0x0100, {4: 6, 8: 7, 16: 8}[es], count, blocklen, stride_bytes, 0) + \
+        struct.pack("<HHIQqq", 0, 1, 1, 0, size, 0)
+    return mxompi.Datatype(desc, 2, size, 0, count * stride_bytes)
+
+
+def ddt_leg(out):
+    import torch
+    import mxompi
+    mxompi.init(0)
+    comm = mxompi.Comm.local(N)
+    st = torch.cuda.current_stream().cuda_stream
+    shapes = [("W16 blen 64/stride 128", _vector(16, 8, 4, 128), _vector(16, 8, 4, 128)),
+              ("W8  blen 8/stride 16", _vector(8, 64, 1, 16), _vector(8, 64, 1, 16)),
+              ("W4  blen 4/stride 8 -> flat", _vector(4, 128, 1, 8), None)]
+    lines = [f"# exchange_bw --ddt: local communicator, n = {N}, {torch.cuda.get_device_name(0)}",
+             "# GB/s = 2 x payload / median call time (host clock, every case ends in a synchronise); "
+             "share = of 6.29 TB/s (float4 copy)",
+             f"{'pair':>10} {'shape':<28} {'case':<30} {'payload MiB':>12} {'us':>10} {'GB/s':>9} {'vs (p)':>7} {'share':>6}"]
+    for S in (256 << 10, 32 << 20):
+        for name, sdt, rdt in shapes:
+            scount = S // sdt.size
+            rcount = S // rdt.size if rdt else S
+            sspan, rspan = N * scount * sdt.extent, N * rcount * (rdt.extent if rdt else 1)
+            sb = [torch.empty(sspan + 64, dtype=torch.uint8, device="cuda").random_(0, 256) for _ in range(N)]
+            rb = [torch.empty(rspan + 64, dtype=torch.uint8, device="cuda").zero_() for _ in range(N)]
+            rb2 = [torch.empty(rspan + 64, dtype=torch.uint8, device="cuda").zero_() for _ in range(N)]
+            ps = [torch.empty(N * S, dtype=torch.uint8, device="cuda") for _ in range(N)]
+            pr = [torch.empty(N * S, dtype=torch.uint8, device="cuda") for _ in range(N)]
+            sp, rp, rp2 = (mxompi._ptrs([t.data_ptr() for t in b]) for b in (sb, rb, rb2))
+            pp, qp = mxompi._ptrs([t.data_ptr() for t in ps]), mxompi._ptrs([t.data_ptr() for t in pr])
+
+            def fused():
+                comm.alltoall_ddt_local(sp, scount, sdt, rp, rcount, rdt, st)
+
+            def composed():
+                for i in range(N):
+                    sdt.pack(N * scount, sb[i].data_ptr(), ps[i].data_ptr(), stream=st)
+                comm.alltoall_local(pp, qp, S, st)
+                if rdt:   # (a flat receive side: the exchanged bytes are the result)
+                    for i in range(N):
+                        rdt.unpack(N * rcount, rb2[i].data_ptr(), pr[i].data_ptr(), stream=st)
+                torch.cuda.synchronize()
+
+            def kcopy():
+                comm.allgather_local(pp, qp, S, st)
+
+            ref = None
+            for case, fn in (("(p) pack+alltoall+unpack", composed), ("(f) alltoall_ddt_local fused", fused),
+                             ("(k) allgather_local (k_copy)", kcopy)):
+                t, gbs = _time(fn, N * N * S)
+                ref = ref or gbs
+                lines.append(f"{S:>10} {name:<28} {case:<30} {N * N * S / 2**20:>12.2f} {t * 1e6:>10.1f} {gbs:>9.1f} "
+                             f"{gbs / ref:>7.2f} {100 * gbs * 1e9 / COPY_RATE:>5.1f}%")
+            fused()
+            composed()
+            for i in range(N):   # both routes moved the same bytes
+                assert torch.equal(rb[i], rb2[i]) if rdt else torch.equal(rb[i][:N * S], pr[i]), "fused != composed"
+            del sb, rb, rb2, ps, pr
+            torch.cuda.empty_cache()
+    comm.close()
+    text = "\n".join(lines) + "\n"
+    print(text, end="")
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
+    ap.add_argument("--ddt", action="store_true", help="time the strided exchange against its composition")
     args = ap.parse_args()
+    if args.ddt:
+        import torch
+        if not torch.cuda.is_available():
+            sys.exit("exchange_bw: no GPU")
+        return ddt_leg(args.out)
     import torch
     import mxompi
     if not torch.cuda.is_available():

@@ -359,10 +359,19 @@ static_assert(std::atomic<uint64_t>::is_always_lock_free, "shared-memory atomics
 // alltoallv (xrow_exchange): every rank publishes the row it sends by, (offsets, sizes) -- one
 // host round like tune_exchange.
 // Two banks, call k in bank k % 2, for the reason reg_exchange gives.
+// the strided forms (mx_alltoallv_ddt) add the send layout, the lower bound
+// of the send span the rank registers, its access units and its verdict
+struct XRowExt {
+  XLay slay;
+  int64_t lo;
+  uint32_t sunit, runit;
+  int32_t verdict, pad;
+};
 struct XRow {
   std::atomic<uint64_t> seq;
-  uint64_t flags;   // bits 0-3: the send buffer's address mod 16; bit 4: the rank calls in place
+  uint64_t flags;   // bits 0-3: the send buffer's address mod 16; bit 4: the rank calls in place; bit 5: a strided form
   uint64_t bytes[MAXR], offs[MAXR];
+  XRowExt e;
 };
 static size_t reg_page_bytes(int n) { return 2 * (size_t)n * sizeof(RegRec) + 2 * (size_t)n * sizeof(XRow); }
 
@@ -396,10 +405,10 @@ static std::vector<Deferred> g_graveyard;
 // exchange counters (mx_comm_exchange_stats): per communicator and, for a
 // caller that cannot reach the communicator (an MPI program above the coll
 // component), summed over the process
-static std::atomic<uint64_t> g_xst[4];
-static void xcount(mx_comm *c, int k) {
-  c->xst[k]++;
-  g_xst[k].fetch_add(1, std::memory_order_relaxed);
+static std::atomic<uint64_t> g_xst[4], g_xdst[4];   // byte forms, strided forms
+static void xcount(mx_comm *c, int k, bool ddt = false) {
+  (ddt ? c->xdst : c->xst)[k]++;
+  (ddt ? g_xdst : g_xst)[k].fetch_add(1, std::memory_order_relaxed);
 }
 
 static void live_add(mx_comm *c) {
@@ -1448,6 +1457,131 @@ extern "C" int mx_allgatherv_local(mx_comm_t *c, const void *const *sbufs, void 
   return finish(c, s);
 }
 
+// ---- the strided forms (k_exchange_vec, mx_exchange_vec.hip) -----------------
+// a pointer moved by a signed byte offset kept modulo 2^64
+static inline char *padd(const char *p, uint64_t off) { return (char *)((uintptr_t)p + (uintptr_t)off); }
+// One side of a call: the layout the kernel reads or writes by, the stream
+// bytes and the extent of one instance.  A NULL datatype is bytes.
+struct XDSide {
+  XLay lay;
+  size_t size;
+  int64_t ext;
+  const DdtLayout *L;
+  bool ok;   // the datatype qualifies (mx_ddt_strided)
+};
+static XDSide xd_side(const mx_ddt_t *d, bool receive_side) {
+  XDSide sd{xlay_flat(), 1, 1, nullptr, true};
+  if (!d) return sd;
+  sd.ok = false;
+  if (d == MX_DDT_NONE) return sd;
+  sd.L = ddt_layout(d);
+  sd.size = sd.L->size;
+  sd.ext = sd.L->ub - sd.L->lb;
+  sd.ok = sd.size && xlay_from(*sd.L, receive_side, &sd.lay);
+  return sd;
+}
+// widens [*lo, *hi) by the bytes `count` instances `displ` extents in touch
+static void xd_span(const XDSide &sd, size_t count, int64_t displ, int64_t *lo, int64_t *hi) {
+  if (!count) return;
+  int64_t a = 0, b = (int64_t)count;
+  if (sd.L) ddt_span(*sd.L, count, &a, &b);
+  *lo = std::min(*lo, a + displ * sd.ext);
+  *hi = std::max(*hi, b + displ * sd.ext);
+}
+// the access unit of one rank's side: layout, address, every block's offset and length
+static unsigned xd_unit(const XDSide &sd, const void *buf, int n, const size_t *counts, const int64_t *displs) {
+  unsigned u = xlay_unit(sd.lay, (uintptr_t)buf);
+  for (int p = 0; p < n; p++) {
+    if (!counts[p]) continue;
+    u = xunit_of(xabs(displs[p] * sd.ext), u);
+    u = xunit_of((uint64_t)counts[p] * sd.size, u);
+  }
+  return u;
+}
+static bool xd_counts_ok(const XDSide &sd, int n, const size_t *counts) {
+  for (int p = 0; p < n; p++)
+    if (sd.size && counts[p] > (((size_t)1 << 47) / sd.size)) return false;
+  return true;
+}
+
+extern "C" int mx_alltoallv_ddt_local(mx_comm_t *c, const void *const *sbufs, const size_t *scounts,
+                                      const int64_t *sdispls, const mx_ddt_t *sddt, void *const *rbufs,
+                                      const size_t *rcounts, const int64_t *rdispls, const mx_ddt_t *rddt,
+                                      void *stream) {
+  if (!c || !c->local || !rbufs || !rcounts || !rdispls) return MX_ERR_ARG;
+  const int n = c->size;
+  const bool inplace = !sbufs || sbufs[0] == MX_IN_PLACE;
+  if (inplace) { scounts = rcounts; sdispls = rdispls; sddt = rddt; }   // the receive description serves both sides
+  else if (!scounts || !sdispls) return MX_ERR_ARG;
+  const XDSide S = xd_side(sddt, false), R = xd_side(rddt, true);
+  if (!S.ok || !R.ok) return MX_ERR_UNSUPPORTED;
+  if (!xd_counts_ok(S, n * n, scounts) || !xd_counts_ok(R, n * n, rcounts)) return MX_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  // every job is planned before any is launched: a word below 4 bytes anywhere declines the call
+  std::vector<XVJob> jobs, first;
+  std::vector<size_t> tmp_off;
+  size_t total = 0;
+  for (int i = 0; i < n; i++)
+    for (int j = 0; j < n; j++) {
+      const size_t ij = (size_t)i * n + j, ji = (size_t)j * n + i;
+      const size_t len = std::min(scounts[ij] * S.size, rcounts[ji] * R.size);   // never past the receiver's room
+      if (!len || (inplace && i == j)) continue;
+      const char *src = padd((const char *)(inplace ? rbufs[i] : sbufs[i]), (uint64_t)(sdispls[ij] * S.ext));
+      char *dst = padd((const char *)rbufs[j], (uint64_t)(rdispls[ji] * R.ext));
+      XVJob jb;
+      int rc;
+      if (inplace) {
+        // every block is read and overwritten by the same call: the sent
+        // blocks go through a flat temporary first (offsets known after the loop)
+        XVJob f;
+        if ((rc = xvjob_make(src, S.lay, 0, (char *)(uintptr_t)16, xlay_flat(), 0, len, &f))) return rc;
+        if ((rc = xvjob_make((const char *)(uintptr_t)16, xlay_flat(), 0, dst, R.lay, 0, len, &jb))) return rc;
+        first.push_back(f);
+        tmp_off.push_back(total);
+        total += (len + 255) & ~(size_t)255;
+      } else if ((rc = xvjob_make(src, S.lay, 0, dst, R.lay, 0, len, &jb))) {
+        return rc;
+      }
+      jobs.push_back(jb);
+    }
+  if (int orc = order(c, s)) return orc;
+  xcount(c, 0, true);
+  char *tmp = nullptr;
+  int rc = MX_SUCCESS;
+  if (inplace && !jobs.empty()) {
+    if (hipMallocAsync((void **)&tmp, total, s) != hipSuccess) return MX_ERR_NOMEM;
+    for (size_t q = 0; q < jobs.size(); q++) {
+      first[q].dst = tmp + tmp_off[q];
+      jobs[q].src = tmp + tmp_off[q];
+    }
+    rc = exchange_vec_launch(first.data(), first.size(), c->poison, s);
+  }
+  if (!rc) rc = exchange_vec_launch(jobs.data(), jobs.size(), c->poison, s);
+  if (tmp) (void)hipFreeAsync(tmp, s);
+  if (rc) return rc;
+  return finish(c, s);
+}
+
+extern "C" int mx_alltoall_ddt_local(mx_comm_t *c, const void *const *sbufs, size_t scount, const mx_ddt_t *sddt,
+                                     void *const *rbufs, size_t rcount, const mx_ddt_t *rddt, void *stream) {
+  if (!c || !c->local) return MX_ERR_ARG;
+  const int n = c->size;
+  std::vector<size_t> sc((size_t)n * n, scount), rc((size_t)n * n, rcount);
+  std::vector<int64_t> sd((size_t)n * n), rd((size_t)n * n);
+  for (int i = 0; i < n; i++)
+    for (int j = 0; j < n; j++) {
+      sd[(size_t)i * n + j] = (int64_t)j * (int64_t)scount;
+      rd[(size_t)i * n + j] = (int64_t)j * (int64_t)rcount;
+    }
+  return mx_alltoallv_ddt_local(c, sbufs, sc.data(), sd.data(), sddt, rbufs, rc.data(), rd.data(), rddt, stream);
+}
+
+extern "C" int mx_comm_exchange_ddt_stats(mx_comm_t *c, uint64_t out[4]) {
+  if (!out) return MX_ERR_ARG;
+  for (int k = 0; k < 4; k++) out[k] = c ? c->xdst[k] : g_xdst[k].load(std::memory_order_relaxed);
+  return MX_SUCCESS;
+}
+
 extern "C" int mx_comm_exchange_stats(mx_comm_t *c, uint64_t out[4]) {
   if (!out) return MX_ERR_ARG;
   for (int k = 0; k < 4; k++) out[k] = c ? c->xst[k] : g_xst[k].load(std::memory_order_relaxed);
@@ -2332,15 +2466,24 @@ struct XCall {
   size_t max_pair;             // the largest block any rank sends
   size_t zc_bytes;             // the size the zero-copy threshold sees
   bool inplace;
+  // the strided forms: offsets are displacement x extent (signed, kept modulo
+  // 2^64), lengths stream bytes, and sb / rb the `user` pointers of the layouts
+  bool ddt;
+  XLay slay, rlay;             // my send / receive layout
+  XLay peer_slay[MAXR];        // p's send layout (what a zero-copy pull reads by)
+  int64_t sb_lo, rb_lo;        // where the spans sb_span / rb_span start, from sb / rb
+  int64_t peer_lo[MAXR];       // p's sb_lo
 };
 
 
-static int xrow_exchange(mx_comm *c, const size_t *bytes, const size_t *offs, uint64_t flags, const XRow **rows) {
+static int xrow_exchange(mx_comm *c, const size_t *bytes, const size_t *offs, uint64_t flags, const XRow **rows,
+                         const XRowExt *ext = nullptr) {
   const int n = c->size;
   const uint64_t k = ++c->xrow_seq;
   XRow *X = (XRow *)((char *)c->reg_shm + 2 * (size_t)n * sizeof(RegRec)) + (k & 1) * (size_t)n;
   XRow &me = X[c->rank];
   me.flags = flags;
+  if (ext) me.e = *ext;
   for (int p = 0; p < n; p++) {
     me.bytes[p] = bytes[p];
     me.offs[p] = offs[p];
@@ -2368,29 +2511,44 @@ static int exchange_mp(mx_comm *c, const XCall &x, hipStream_t s) {
   DoneMark dm;   // the call's last DONE signal raises the completion word
   done_mark_arm(c, dm);
   const int n = c->size, r = c->rank;
-  xcount(c, 0);
+  xcount(c, 0, x.ddt);
   if (!x.max_pair) return MX_SUCCESS;   // nothing moves on any rank
   const size_t self_len = std::min(x.send_len[r], x.recv_len[r]);
   XJob jobs[MAXR];
+  XVJob vjobs[MAXR];
   int nj, rc;
+  // the strided forms: the same jobs with a layout on either side
+  auto vadd = [&](const char *src, const XLay &sl, uint64_t pos_s, char *dst, const XLay &dl, uint64_t pos_d,
+                  size_t len) { return len ? xvjob_make(src, sl, pos_s, dst, dl, pos_d, len, &vjobs[nj++]) : MX_SUCCESS; };
+  const XLay flat = xlay_flat();
   if (!x.inplace && zc_allowed(c, ZC_DEFAULT, x.zc_bytes)) {
     // zero-copy: rank r pulls its block from every peer's registered sbuf
     // straight into its rbuf (remote reads, local writes only).  The kernel
     // takes any pair of alignments, so the ranks need not agree on one.
     const char *ps[MAXR];
     char *pr[MAXR];
-    const int zc = reg_exchange(c, x.sb, x.sb_span, x.rb, x.rb_span, 0, true, ps, pr);
+    // (the strided forms register the true spans: sb_lo / rb_lo may be negative)
+    const int zc = reg_exchange(c, padd(x.sb, x.sb_lo), x.sb_span, padd(x.rb, x.rb_lo), x.rb_span, 0, true, ps, pr);
     if (zc < 0) return zc;
     if (zc) {
       const uint64_t g = ++c->gen;
-      xcount(c, 1);
+      xcount(c, 1, x.ddt);
       if ((rc = signal_wait_all(c, FLAG_READY, g << 1, g << 1, s))) return rc;   // every sbuf holds its blocks
       nj = 0;
-      for (int p = 0; p < n; p++)
-        if (p != r) jobs[nj++] = XJob{ps[p] + x.pull_off[p], x.rb + x.recv_off[p], x.recv_len[p]};
-      if (x.sb + x.send_off[r] != x.rb + x.recv_off[r])
-        jobs[nj++] = XJob{x.sb + x.send_off[r], x.rb + x.recv_off[r], self_len};
-      if ((rc = exchange_launch(jobs, nj, c->poison, s))) return rc;
+      if (x.ddt) {   // both sides strided, the source layout from the peer's row
+        for (int p = 0; p < n && !rc; p++)
+          if (p != r)
+            rc = vadd(padd(ps[p], x.pull_off[p] - (uint64_t)x.peer_lo[p]), x.peer_slay[p], 0, padd(x.rb, x.recv_off[p]),
+                      x.rlay, 0, x.recv_len[p]);
+        if (!rc) rc = vadd(padd(x.sb, x.send_off[r]), x.slay, 0, padd(x.rb, x.recv_off[r]), x.rlay, 0, self_len);
+        if (rc || (rc = exchange_vec_launch(vjobs, nj, c->poison, s))) return rc;
+      } else {
+        for (int p = 0; p < n; p++)
+          if (p != r) jobs[nj++] = XJob{ps[p] + x.pull_off[p], x.rb + x.recv_off[p], x.recv_len[p]};
+        if (x.sb + x.send_off[r] != x.rb + x.recv_off[r])
+          jobs[nj++] = XJob{x.sb + x.send_off[r], x.rb + x.recv_off[r], self_len};
+        if ((rc = exchange_launch(jobs, nj, c->poison, s))) return rc;
+      }
       if ((rc = signal_wait_all(c, FLAG_PUSHED, g, g, s))) return rc;   // done reading the peers' sbufs
       if ((rc = signal_done(c, g, s, &dm))) return rc;
       return finish_done(c, s, dm);
@@ -2409,13 +2567,37 @@ static int exchange_mp(mx_comm *c, const XCall &x, hipStream_t s) {
   size_t slot, cap;
   if (!xstage_slots(c->main_bytes, n, &slot, &cap)) return MX_ERR_NOMEM;
   const uint64_t rounds = xrounds(x.max_pair, cap);
-  xcount(c, 2);
+  xcount(c, 2, x.ddt);
   for (uint64_t q = 0; q < rounds; q++) {
     const uint64_t g = ++c->gen;
     size_t o, l;
-    xcount(c, 3);
+    xcount(c, 3, x.ddt);
     if ((rc = wait_all(c, FLAG_DONE, g - 1, s))) return rc;
     nj = 0;
+    if (x.ddt) {
+      // strided -> flat slot, then flat slot -> strided.  A round cuts every
+      // pair's stream at q * cap (a multiple of 256), inside a block or an
+      // instance as it falls; the slots start 256-byte aligned.
+      rc = MX_SUCCESS;
+      for (int p = 0; p < n && !rc; p++) {
+        if (p == r) continue;
+        xround_piece(x.send_len[p], cap, q, &o, &l);
+        rc = vadd(padd(x.sb, x.send_off[p]), x.slay, o, c->peer_staging[p] + (size_t)r * slot, flat, 0, l);
+      }
+      xround_piece(self_len, cap, q, &o, &l);
+      if (!rc && !x.inplace) rc = vadd(padd(x.sb, x.send_off[r]), x.slay, o, padd(x.rb, x.recv_off[r]), x.rlay, o, l);
+      if (rc || (rc = exchange_vec_launch(vjobs, nj, c->poison, s))) return rc;
+      if ((rc = signal_wait_all(c, FLAG_READY, g << 1, g << 1, s))) return rc;
+      nj = 0;
+      for (int p = 0; p < n && !rc; p++) {
+        if (p == r) continue;
+        xround_piece(x.recv_len[p], cap, q, &o, &l);
+        rc = vadd(c->staging + (size_t)p * slot, flat, 0, padd(x.rb, x.recv_off[p]), x.rlay, o, l);
+      }
+      if (rc || (rc = exchange_vec_launch(vjobs, nj, c->poison, s))) return rc;
+      if ((rc = signal_done(c, g, s, q + 1 == rounds ? &dm : nullptr))) return rc;
+      continue;
+    }
     for (int p = 0; p < n; p++) {
       if (p == r) continue;
       xround_piece(x.send_len[p], cap, q, &o, &l);
@@ -2569,6 +2751,111 @@ extern "C" int mx_alltoallv(mx_comm_t *c, const void *sbuf, const size_t *sbytes
   x.zc_bytes = (size_t)n * x.max_pair;
   if (c->xmin && x.zc_bytes <= c->xmin) return MX_ERR_UNSUPPORTED;   // the same on every rank
   return exchange_mp(c, x, s);
+}
+
+// The strided forms.  Every rank takes part in the row exchange whatever it
+// thinks of its own datatypes, so a refusal anywhere is every rank's return
+// value and nobody is left waiting.
+extern "C" int mx_alltoallv_ddt(mx_comm_t *c, const void *sbuf, const size_t *scounts, const int64_t *sdispls,
+                                const mx_ddt_t *sddt, void *rbuf, const size_t *rcounts, const int64_t *rdispls,
+                                const mx_ddt_t *rddt, void *stream) {
+  if (!c || (c->local && c->size != 1)) return c && c->local ? MX_ERR_STATE : MX_ERR_ARG;
+  const int n = c->size, r = c->rank;
+  if (!rcounts || !rdispls) return MX_ERR_ARG;
+  XCall x;
+  memset(&x, 0, sizeof x);
+  x.ddt = true;
+  x.inplace = sbuf == MX_IN_PLACE;
+  if (x.inplace) { scounts = rcounts; sdispls = rdispls; sddt = rddt; }
+  else if (!scounts || !sdispls) return MX_ERR_ARG;
+  const XDSide S = xd_side(sddt, false), R = xd_side(rddt, true);
+  if (!xd_counts_ok(S, n, scounts) || !xd_counts_ok(R, n, rcounts)) return MX_ERR_ARG;
+  size_t stotal = 0, rtotal = 0;
+  for (int p = 0; p < n; p++) { stotal += scounts[p]; rtotal += rcounts[p]; }
+  if ((!rbuf && rtotal) || (!x.inplace && !sbuf && stotal)) return MX_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = exchange_enter(c, s)) return rc;
+  x.rb = (char *)rbuf;
+  x.sb = x.inplace ? (const char *)rbuf : (const char *)sbuf;
+  if (!x.sb) x.sb = x.rb;     // nothing to send: any address serves (no byte of it is read)
+  if (!x.rb) x.rb = (char *)x.sb;
+  x.slay = S.lay;
+  x.rlay = R.lay;
+  // a buffer no byte moves through does not count (its address may be anything)
+  const unsigned sunit = S.ok ? xd_unit(S, stotal ? x.sb : nullptr, n, scounts, sdispls) : 0;
+  const unsigned runit = R.ok ? xd_unit(R, rtotal ? x.rb : nullptr, n, rcounts, rdispls) : 0;
+  const bool mine = sunit >= 4 && runit >= 4;
+  if (n == 1) {
+    if (!mine) return MX_ERR_UNSUPPORTED;
+    xcount(c, 0, true);
+    XVJob jb;
+    const size_t len = std::min(scounts[0] * S.size, rcounts[0] * R.size);
+    const char *src = padd(x.sb, (uint64_t)(sdispls[0] * S.ext));
+    char *dst = padd(x.rb, (uint64_t)(rdispls[0] * R.ext));
+    if (len && !x.inplace) {
+      if (int rc = xvjob_make(src, S.lay, 0, dst, R.lay, 0, len, &jb)) return rc;
+      if (int rc = exchange_vec_launch(&jb, 1, c->poison, s)) return rc;
+    }
+    return finish(c, s);
+  }
+  if (!c->reg_shm) return MX_ERR_UNSUPPORTED;   // agreed at creation: every rank returns here
+  // the spans this rank would register (the true bounds of what the call touches)
+  int64_t slo = INT64_MAX, shi = INT64_MIN, rlo = INT64_MAX, rhi = INT64_MIN;
+  size_t sbytes[MAXR], soffs[MAXR];
+  for (int p = 0; p < n; p++) {
+    sbytes[p] = S.ok ? scounts[p] * S.size : 0;
+    soffs[p] = S.ok ? (size_t)(sdispls[p] * S.ext) : 0;
+    if (S.ok) xd_span(S, scounts[p], sdispls[p], &slo, &shi);
+    if (R.ok) xd_span(R, rcounts[p], rdispls[p], &rlo, &rhi);
+  }
+  if (slo > shi) slo = shi = 0;
+  if (rlo > rhi) rlo = rhi = 0;
+  XRowExt e;
+  memset(&e, 0, sizeof e);
+  e.slay = S.lay;
+  e.lo = slo;
+  e.sunit = sunit;
+  e.runit = runit;
+  e.verdict = mine;
+  const XRow *rows = nullptr;
+  if (int rc = xrow_exchange(c, sbytes, soffs, (x.inplace ? 16 : 0) | 32, &rows, &e)) return rc;
+  bool all = true;
+  for (int p = 0; p < n; p++) {
+    if (!(rows[p].flags & 32) || ((rows[p].flags >> 4) & 1) != (uint64_t)x.inplace) return MX_ERR_ARG;   // every rank sees it
+    all = all && rows[p].e.verdict && rows[p].e.sunit >= 4 && rows[p].e.runit >= 4;
+  }
+  if (!all) return MX_ERR_UNSUPPORTED;   // the same on every rank, before any byte moves
+  for (int p = 0; p < n; p++) {
+    x.send_off[p] = soffs[p];
+    x.send_len[p] = sbytes[p];
+    x.pull_off[p] = (size_t)rows[p].offs[r];
+    x.peer_slay[p] = rows[p].e.slay;
+    x.peer_lo[p] = rows[p].e.lo;
+    x.recv_off[p] = (size_t)(rdispls[p] * R.ext);
+    x.recv_len[p] = std::min((size_t)rows[p].bytes[r], rcounts[p] * R.size);   // never past the receiver's room
+    for (int q = 0; q < n; q++) x.max_pair = std::max(x.max_pair, (size_t)rows[p].bytes[q]);
+  }
+  x.sb_lo = slo;
+  x.sb_span = (size_t)(shi - slo);
+  x.rb_lo = rlo;
+  x.rb_span = (size_t)(rhi - rlo);
+  x.zc_bytes = (size_t)n * x.max_pair;
+  if (c->xmin && x.zc_bytes <= c->xmin) return MX_ERR_UNSUPPORTED;   // the same on every rank
+  return exchange_mp(c, x, s);
+}
+
+extern "C" int mx_alltoall_ddt(mx_comm_t *c, const void *sbuf, size_t scount, const mx_ddt_t *sddt, void *rbuf,
+                               size_t rcount, const mx_ddt_t *rddt, void *stream) {
+  if (!c || c->size < 1 || c->size > MAXR) return MX_ERR_ARG;
+  size_t sc[MAXR], rc[MAXR];
+  int64_t sd[MAXR], rd[MAXR];
+  for (int p = 0; p < c->size; p++) {
+    sc[p] = scount;
+    rc[p] = rcount;
+    sd[p] = (int64_t)p * (int64_t)scount;
+    rd[p] = (int64_t)p * (int64_t)rcount;
+  }
+  return mx_alltoallv_ddt(c, sbuf ? sbuf : MX_IN_PLACE, sc, sd, sddt, rbuf, rc, rd, rddt, stream);
 }
 
 // MPI_Bcast, all-peer scatter + allgather (the reference's large-message

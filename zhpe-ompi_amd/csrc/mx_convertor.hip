@@ -39,6 +39,7 @@
 #include "../../include/mx_convertor.h"
 #include "mx_env.hpp"
 #include "mx_ddt_layout.hpp"
+#include "mx_exchange_vec_plan.hpp"
 
 namespace mx {
 
@@ -264,7 +265,6 @@ __global__ void __launch_bounds__(kCB) k_convert(ConvArgs a) {
 // kVIt words per lane are loaded before any is stored.
 // ---------------------------------------------------------------------------
 constexpr int kVIt = 8;
-constexpr uint64_t kVecMaxBlen = (uint64_t)1 << 22;   // keeps t / blen exact in fp32 + 1 correction
 
 template <int W, bool PACK, bool NT = false>
 __global__ void __launch_bounds__(kCB) k_convert_vec(ConvArgs a, DRun R, float rblen) {
@@ -2054,6 +2054,13 @@ extern "C" int mx_ddt_span(const mx_ddt_t *d, size_t count, int64_t *lo, int64_t
   return MX_SUCCESS;
 }
 
+namespace mx {
+const DdtLayout *ddt_layout(const mx_ddt *d) { return d ? &d->lay : nullptr; }
+}
+extern "C" int mx_ddt_strided(const mx_ddt_t *d, int receive_side) {
+  XLay l;
+  return d && d != MX_DDT_NONE && xlay_from(d->lay, receive_side != 0, &l) ? 1 : 0;
+}
 extern "C" int mx_ddt_last_path(const mx_ddt_t *d) { return d ? d->last_path.load(std::memory_order_relaxed) : PATH_NONE; }
 
 // ---------------------------------------------------------------------------

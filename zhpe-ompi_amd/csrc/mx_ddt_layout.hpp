@@ -36,6 +36,8 @@ struct DRun {
 
 constexpr int kCB = 256;
 constexpr size_t kMaxRuns = (size_t)1 << 22;
+// VEC kernels (k_convert_vec, k_exchange_vec): keeps t / blen exact in fp32 + 1 correction
+constexpr uint64_t kVecMaxBlen = (uint64_t)1 << 22;
 
 constexpr uint32_t kBmapMaxS = 65535;      // packed bytes per instance (piece soff is 16-bit)
 constexpr size_t kBmapLds = 20480;         // PACK: map bytes staged in LDS

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "mx_exchange_plan.hpp"
+#include "mx_exchange_vec_plan.hpp"
 
 namespace mx {
 
@@ -32,6 +33,14 @@ void xtable_free(XTable *t);
 // as one launch through `tab`; without one, as launches of kXInline jobs.
 int exchange_launch(const XJob *jobs, size_t n, const int *poison, hipStream_t s, XTable *tab = nullptr);
 
+// the layout of a committed datatype (mx_convertor.hip)
+const DdtLayout *ddt_layout(const mx_ddt *d);
+
+// The strided exchange kernel (mx_exchange_vec.hip): enqueues jobs made by
+// xvjob_make on `s`, one launch per word width and kXInline jobs; jobs whose
+// two sides are flat go to exchange_launch.  No two jobs may write the same byte.
+int exchange_vec_launch(const XVJob *jobs, size_t n, const int *poison, hipStream_t s);
+
 }  // namespace mx
 
 // For the tests (not part of include/mx_coll.h): the destination bytes one
@@ -43,3 +52,7 @@ extern "C" int mx_exchange_geometry(size_t *block_bytes, size_t *wave_bytes);
 // XTables alive in this process: a communicator's goes back to the pools when it is destroyed
 extern "C" int mx_exchange_tables_live(void);
 extern "C" long long mx_comm_exchange_rounds(const mx_comm_t *comm, size_t max_pair);
+// k_exchange_vec: the stream bytes one workgroup and one wave step move at
+// word width W (4, 8, 16), and the jobs this process launched at W = 4, 8, 16
+extern "C" int mx_exchange_vec_geometry(unsigned W, size_t *block_bytes, size_t *wave_bytes);
+extern "C" int mx_exchange_vec_widths(uint64_t out[3]);

@@ -7,6 +7,22 @@
 
 namespace mx {
 
+uint64_t xplan_tables(const uint64_t *nb, size_t J, uint64_t max_grid_blocks, std::vector<XSeg> &seg,
+                      std::vector<XLaunch> &launch) {
+  seg.resize(J + 1);
+  launch.clear();
+  uint64_t blocks = 0, round = 0;
+  for (size_t i = 0; i < J; i++) {
+    seg[i] = XSeg{blocks, round};
+    blocks += (nb[i] - round) * (uint64_t)(J - i);   // rounds [round, nb[i]) hold the jobs i..J-1
+    round = nb[i];
+  }
+  seg[J] = XSeg{blocks, round};
+  for (uint64_t b = 0; b < blocks; b += max_grid_blocks)
+    launch.push_back(XLaunch{b, (uint32_t)std::min<uint64_t>(max_grid_blocks, blocks - b)});
+  return blocks;
+}
+
 int xplan_build(const XJob *jobs, size_t n, XPlan &out, uint64_t max_grid_blocks) {
   out = XPlan();
   if (n > (size_t)kXMaxJobs || (n && !jobs) || !max_grid_blocks) return MX_ERR_ARG;
@@ -20,19 +36,9 @@ int xplan_build(const XJob *jobs, size_t n, XPlan &out, uint64_t max_grid_blocks
   std::stable_sort(out.jobs.begin(), out.jobs.end(), [](const XJob &a, const XJob &b) {
     return xjob_blocks((uintptr_t)a.dst, a.bytes) < xjob_blocks((uintptr_t)b.dst, b.bytes);
   });
-  const size_t J = out.jobs.size();
-  out.seg.resize(J + 1);
-  uint64_t blocks = 0, round = 0;
-  for (size_t i = 0; i < J; i++) {
-    out.seg[i] = XSeg{blocks, round};
-    const uint64_t nb = xjob_blocks((uintptr_t)out.jobs[i].dst, out.jobs[i].bytes);
-    blocks += (nb - round) * (uint64_t)(J - i);   // rounds [round, nb) hold the jobs i..J-1
-    round = nb;
-  }
-  out.seg[J] = XSeg{blocks, round};
-  out.nblocks = blocks;
-  for (uint64_t b = 0; b < blocks; b += max_grid_blocks)
-    out.launch.push_back(XLaunch{b, (uint32_t)std::min<uint64_t>(max_grid_blocks, blocks - b)});
+  std::vector<uint64_t> nb(out.jobs.size());
+  for (size_t i = 0; i < nb.size(); i++) nb[i] = xjob_blocks((uintptr_t)out.jobs[i].dst, out.jobs[i].bytes);
+  out.nblocks = xplan_tables(nb.data(), nb.size(), max_grid_blocks, out.seg, out.launch);
   return MX_SUCCESS;
 }
 

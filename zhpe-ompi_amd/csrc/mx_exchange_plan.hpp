@@ -95,6 +95,11 @@ MX_XHD inline void xplan_lookup(SegPtr seg, uint32_t njobs, uint64_t b, uint32_t
   }
 }
 
+// The segment and launch tables of J jobs with ascending block counts nb[0..J);
+// returns the blocks in all.
+uint64_t xplan_tables(const uint64_t *nb, size_t J, uint64_t max_grid_blocks, std::vector<XSeg> &seg,
+                      std::vector<XLaunch> &launch);
+
 // Builds the plan of one launch group from `n` jobs (empty jobs dropped).
 // max_grid_blocks: the launch split (kXMaxGridBlocks; tests pass less).
 int xplan_build(const XJob *jobs, size_t n, XPlan &out, uint64_t max_grid_blocks = kXMaxGridBlocks);

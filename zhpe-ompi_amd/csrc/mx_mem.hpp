@@ -60,6 +60,25 @@ __device__ __forceinline__ void st16(V *p, const V &v) {
   }
 }
 
+// One aligned W-byte word (4, 8 or 16) through a global_* access with the
+// same two policies, for kernels whose word width follows the data's layout.
+template <int W> struct gword;
+template <> struct gword<4> { typedef uint32_t T; };
+template <> struct gword<8> { typedef uint32_t T __attribute__((ext_vector_type(2))); };
+template <> struct gword<16> { typedef u32x4 T; };
+template <bool NT, int W>
+__device__ __forceinline__ typename gword<W>::T ldw(const char *p) {
+  const __attribute__((address_space(1))) typename gword<W>::T *q = gp(reinterpret_cast<const typename gword<W>::T *>(p));
+  if constexpr (NT) return __builtin_nontemporal_load(q);
+  else return *q;
+}
+template <bool NT, int W>
+__device__ __forceinline__ void stw(char *p, typename gword<W>::T v) {
+  __attribute__((address_space(1))) typename gword<W>::T *q = gp(reinterpret_cast<typename gword<W>::T *>(p));
+  if constexpr (NT) __builtin_nontemporal_store(v, q);
+  else *q = v;
+}
+
 // true if a launch whose streams together touch `bytes` should use nt accesses
 bool mx_nt_for(size_t bytes);
 

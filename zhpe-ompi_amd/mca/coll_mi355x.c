@@ -812,8 +812,27 @@ static int mx_coll_allgather(const void *sbuf, int scount, struct ompi_datatype_
  * displacements then scale to bytes by the type size); every other call --
  * host buffers, derived layouts, small calls, MX_ERR_UNSUPPORTED from the
  * library -- runs on the saved module through host views of the device
- * buffers.  All of these must hold alike on every rank of a call. */
+ * buffers.  All of these must hold alike on every rank of a call.
+ *
+ * alltoall and alltoallv with a datatype that is not contiguous (a vector, a
+ * resized type: transposes, halo columns) go to the library's strided forms
+ * (mx_alltoall_ddt / mx_alltoallv_ddt, one fused kernel) under the same
+ * conditions.  Whether a call has a non-contiguous datatype must hold alike
+ * on every rank, as contiguity must above: the strided forms open with a row
+ * exchange of their own that every rank has to enter.  A datatype the host
+ * cannot describe travels as MX_DDT_NONE, so that rank still takes part and
+ * every rank gets MX_ERR_UNSUPPORTED -- as for layouts the kernel does not
+ * take (two-level, multi-run, indexed, 2-byte blocks) -- and runs the saved
+ * module.  allgatherv, the self slots and the nonblocking and persistent
+ * slots keep to contiguous datatypes. */
 static int xch_contig(struct ompi_datatype_t *dt) { return mx_ompi_host->dtype_contiguous(dt, 2); }
+/* the strided forms' handle of dt (counts stay instances, so a contiguous
+ * type is described too); MX_DDT_NONE: the host cannot describe it */
+static const mx_ddt_t *xch_ddt(mx_coll_module_t *m, struct ompi_datatype_t *dt)
+{
+    mx_ddt_t *h = ddt_for(m, dt);
+    return h ? h : MX_DDT_NONE;
+}
 /* sends / recvs: the rank has bytes to send / receive.  A buffer nothing moves
  * through may be anything (NULL, host memory) and must not change the route,
  * which every rank has to choose alike. */
@@ -873,6 +892,14 @@ static int mx_coll_alltoall(const void *sbuf, int scount, struct ompi_datatype_t
             rc = MX_ERR_ARG;   /* type signatures differ */
         if (!rc) rc = mx_alltoall(m->mx, inplace ? MX_IN_PLACE : sbuf, rbuf, rbytes, m->stream);
         if (rc != MX_ERR_UNSUPPORTED) return map_rc(rc);
+    } else if (rbytes && n <= MX_MAX_RANKS && big(m, rbytes * n) && xch_device(sbuf, 1, rbuf, 1) && comm_ready(m)) {
+        /* a non-contiguous datatype: the strided form */
+        int rc = begin(m);
+        if (!rc)
+            rc = mx_alltoall_ddt(m->mx, inplace ? MX_IN_PLACE : sbuf, (size_t)scount,
+                                 inplace ? NULL : xch_ddt(m, sdtype), rbuf, (size_t)rcount, xch_ddt(m, rdtype),
+                                 m->stream);
+        if (rc != MX_ERR_UNSUPPORTED) return map_rc(rc);
     }
     return host_alltoall(m, sbuf, scount, sdtype, rbuf, rcount, rdtype);
 }
@@ -912,6 +939,22 @@ static int mx_coll_alltoallv(const void *sbuf, const int *scounts, const int *sd
         if (!rc)
             rc = mx_alltoallv(m->mx, inplace ? MX_IN_PLACE : sends ? sbuf : NULL, inplace ? NULL : sb,
                               inplace ? NULL : so, recvs ? rbuf : NULL, rb, ro, m->stream);
+        if (rc != MX_ERR_UNSUPPORTED) return map_rc(rc);
+    } else if (n <= MX_MAX_RANKS && xch_device(sbuf, sends, rbuf, recvs) && comm_ready(m)) {
+        /* a non-contiguous datatype: the strided form, counts and displacements as MPI has them */
+        size_t sc[MX_MAX_RANKS], rc_[MX_MAX_RANKS];
+        int64_t sd[MX_MAX_RANKS], rd[MX_MAX_RANKS];
+        for (int i = 0; i < n; i++) {
+            rc_[i] = rcounts[i] > 0 ? (size_t)rcounts[i] : 0;
+            rd[i] = rdisps[i];
+            sc[i] = !inplace && scounts[i] > 0 ? (size_t)scounts[i] : 0;
+            sd[i] = inplace ? 0 : sdisps[i];
+        }
+        int rc = begin(m);
+        if (!rc)
+            rc = mx_alltoallv_ddt(m->mx, inplace ? MX_IN_PLACE : sends ? sbuf : NULL, sc, sd,
+                                  inplace ? NULL : xch_ddt(m, sdtype), recvs ? rbuf : NULL, rc_, rd,
+                                  xch_ddt(m, rdtype), m->stream);
         if (rc != MX_ERR_UNSUPPORTED) return map_rc(rc);
     }
     return host_alltoallv(m, sbuf, scounts, sdisps, sdtype, rbuf, rcounts, rdisps, rdtype);

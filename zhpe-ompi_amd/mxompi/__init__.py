@@ -315,6 +315,16 @@ def _coll_lib():
         L.mx_exchange_geometry.argtypes = [szp, szp]
         L.mx_comm_exchange_rounds.argtypes = [vp, sz]
         L.mx_comm_exchange_rounds.restype = ctypes.c_longlong
+        i64p = ctypes.POINTER(ctypes.c_int64)
+        L.mx_alltoall_ddt.argtypes = [vp, vp, sz, vp, vp, sz, vp, vp]
+        L.mx_alltoallv_ddt.argtypes = [vp, vp, szp, i64p, vp, vp, szp, i64p, vp, vp]
+        L.mx_alltoall_ddt_local.argtypes = [vp, pp, sz, vp, pp, sz, vp, vp]
+        L.mx_alltoallv_ddt_local.argtypes = [vp, pp, szp, i64p, vp, pp, szp, i64p, vp, vp]
+        L.mx_comm_set_exchange_min.argtypes = [vp, sz]
+        L.mx_comm_exchange_ddt_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
+        L.mx_exchange_vec_geometry.argtypes = [ctypes.c_uint, szp, szp]
+        L.mx_exchange_vec_widths.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
+        L.mx_ddt_strided.argtypes = [vp, i]
         L.mx_bcast_local.argtypes = [vp, pp, sz, i, vp]
         L.mx_allreduce_decision.argtypes = [i, sz, i]
         L.mx_comm_set_profiling.argtypes = [vp, i]
@@ -496,6 +506,49 @@ def exchange_geometry():
     return b.value, w.value
 
 
+def _i64s(v):
+    """An int64 array from a sequence (displacements may be negative)."""
+    if v is None or isinstance(v, ctypes.Array):
+        return v
+    v = [int(x) for x in v]
+    return (ctypes.c_int64 * len(v))(*v)
+
+
+DDT_NONE = 1                       # MX_DDT_NONE: a datatype this rank cannot describe
+_XD_KEYS = ("calls", "zero_copy_calls", "staged_calls", "staged_rounds")
+
+
+def _ddt_h(d):
+    """Datatype, None (bytes) or DDT_NONE as the handle the library takes."""
+    if d is None:
+        return None
+    return ctypes.c_void_p(d) if isinstance(d, int) else d.h
+
+
+def exchange_vec_geometry(width):
+    """(stream bytes one workgroup moves, stream bytes one wave step moves) in
+    the strided exchange kernel at word width `width` (4, 8 or 16)."""
+    b, w = ctypes.c_size_t(), ctypes.c_size_t()
+    check(_coll_lib().mx_exchange_vec_geometry(width, ctypes.byref(b), ctypes.byref(w)), "mx_exchange_vec_geometry")
+    return b.value, w.value
+
+
+def exchange_vec_widths():
+    """Jobs the strided exchange kernel has been launched with in this process,
+    by word width: {4: .., 8: .., 16: ..}."""
+    out = (ctypes.c_uint64 * 3)()
+    check(_coll_lib().mx_exchange_vec_widths(out), "mx_exchange_vec_widths")
+    return dict(zip((4, 8, 16), (int(v) for v in out)))
+
+
+def exchange_ddt_stats_total():
+    """Strided exchange calls of every communicator of this process
+    (mx_comm_exchange_ddt_stats with a null communicator)."""
+    out = (ctypes.c_uint64 * 4)()
+    check(_coll_lib().mx_comm_exchange_ddt_stats(None, out), "mx_comm_exchange_ddt_stats")
+    return dict(zip(_XD_KEYS, (int(v) for v in out)))
+
+
 def exchange_tables_live():
     """Table memories of the exchange kernel alive in this process (a test hook)."""
     return _coll_lib().mx_exchange_tables_live()
@@ -651,6 +704,29 @@ class Comm:
         check(_coll_lib().mx_comm_exchange_stats(self.h, out), "mx_comm_exchange_stats")
         return dict(zip(("calls", "zero_copy_calls", "staged_calls", "staged_rounds"), (int(v) for v in out)))
 
+    # strided exchanges: counts in instances, displacements in extents, a
+    # datatype None = bytes (or DDT_NONE); sbuf None = MPI_IN_PLACE
+    def alltoall_ddt(self, sbuf, scount, sddt, rbuf, rcount, rddt, stream=0):
+        check(_coll_lib().mx_alltoall_ddt(self.h, sbuf, scount, _ddt_h(sddt), rbuf, rcount, _ddt_h(rddt),
+                                          stream or None), "mx_alltoall_ddt")
+
+    def alltoallv_ddt(self, sbuf, scounts, sdispls, sddt, rbuf, rcounts, rdispls, rddt, stream=0):
+        check(_coll_lib().mx_alltoallv_ddt(self.h, IN_PLACE if sbuf is None else sbuf, _sizes(scounts),
+                                           _i64s(sdispls), _ddt_h(sddt), rbuf, _sizes(rcounts), _i64s(rdispls),
+                                           _ddt_h(rddt), stream or None), "mx_alltoallv_ddt")
+
+    def set_exchange_min(self, min_bytes):
+        """alltoallv and the strided forms decline calls of size x largest pair
+        <= min_bytes (mx_comm_set_exchange_min; 0 = never)."""
+        check(_coll_lib().mx_comm_set_exchange_min(self.h, min_bytes), "mx_comm_set_exchange_min")
+
+    def exchange_ddt_stats(self):
+        """Strided exchange calls of this communicator (mx_comm_exchange_ddt_stats):
+        all, zero-copy, staged, and the staging rounds the staged ones took."""
+        out = (ctypes.c_uint64 * 4)()
+        check(_coll_lib().mx_comm_exchange_ddt_stats(self.h, out), "mx_comm_exchange_ddt_stats")
+        return dict(zip(_XD_KEYS, (int(v) for v in out)))
+
     def exchange_rounds(self, max_pair):
         """Staging rounds of a staged exchange whose largest pair is max_pair bytes."""
         rc = _coll_lib().mx_comm_exchange_rounds(self.h, max_pair)
@@ -785,6 +861,18 @@ class Comm:
         sp = _ptrs(sbufs) if sbufs is not None else None
         check(_coll_lib().mx_alltoallv_local(self.h, sp, _sizes(sbytes), _sizes(soffs), _ptrs(rbufs),
                                              _sizes(rbytes), _sizes(roffs), stream or None), "mx_alltoallv_local")
+
+    def alltoall_ddt_local(self, sbufs, scount, sddt, rbufs, rcount, rddt, stream=0):
+        sp = _ptrs(sbufs) if sbufs is not None else None
+        check(_coll_lib().mx_alltoall_ddt_local(self.h, sp, scount, _ddt_h(sddt), _ptrs(rbufs), rcount,
+                                                _ddt_h(rddt), stream or None), "mx_alltoall_ddt_local")
+
+    def alltoallv_ddt_local(self, sbufs, scounts, sdispls, sddt, rbufs, rcounts, rdispls, rddt, stream=0):
+        """The size x size matrices of alltoallv_local, in instances and extents."""
+        sp = _ptrs(sbufs) if sbufs is not None else None
+        check(_coll_lib().mx_alltoallv_ddt_local(self.h, sp, _sizes(scounts), _i64s(sdispls), _ddt_h(sddt),
+                                                 _ptrs(rbufs), _sizes(rcounts), _i64s(rdispls), _ddt_h(rddt),
+                                                 stream or None), "mx_alltoallv_ddt_local")
 
     def allgatherv_local(self, sbufs, rbufs, rbytes, roffs, stream=0):
         sp = _ptrs(sbufs) if sbufs is not None else None
@@ -985,6 +1073,10 @@ class Datatype:
     def last_path(self):
         """Kernel family of the last pack / unpack (mx_ddt_last_path)."""
         return self.PATHS[int(_ddt_lib().mx_ddt_last_path(self.h))]
+
+    def strided(self, receive_side=False):
+        """True if the strided exchanges take this datatype (mx_ddt_strided)."""
+        return bool(_coll_lib().mx_ddt_strided(self.h, 1 if receive_side else 0))
 
     def pack(self, count, user, packed, offset=0, length=None, stream=0):
         length = self.size * count - offset if length is None else length
