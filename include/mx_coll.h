@@ -22,6 +22,11 @@
  *                         gives the same bytes; one exchange kernel moves a
  *                         table of {src, dst, bytes} jobs of any size and
  *                         byte alignment, csrc/mx_exchange.hip)
+ *   mx_gather, mx_gatherv, mx_scatter, mx_scatterv
+ *                      <- coll_basic_gather.c, coll_basic_gatherv.c,
+ *                         coll_basic_scatter.c, coll_basic_scatterv.c (pure
+ *                         data movement: the two exchange kernels under a
+ *                         rooted launch and flag plan, csrc/mx_rooted_plan.hip)
  *
  * Design (MI355X-first, not the reference's message pattern):
  *  * data moves ALL-PEER over xGMI in one step per phase (every GPU writes
@@ -389,6 +394,57 @@ int mx_alltoallv_ddt(mx_comm_t *comm, const void *sbuf, const size_t *scounts, c
  * count them).  comm NULL: the sums over this process's communicators. */
 int mx_comm_exchange_ddt_stats(mx_comm_t *comm, uint64_t out[4]);
 
+/* Rooted exchanges (slots `gather`, `gatherv`, `scatter`, `scatterv`,
+ * coll.h:213-227) on the two exchange kernels.  Each entry point takes
+ * either kind of side: a NULL datatype means bytes (the count is bytes, the
+ * displacement a byte offset), otherwise counts are instances and
+ * displacements multiples of the extent; the qualification is
+ * mx_ddt_strided's.  A pair of two flat sides is a byte job of any length
+ * and alignment; every other pair moves by words of at least 4 bytes.
+ *
+ * The receive arguments of the gathers and the send arguments of the
+ * scatters are read on the root only; elsewhere they may be anything.  In
+ * place follows MPI and concerns the root only: sbuf MX_IN_PLACE on a
+ * gather's root, rbuf MX_IN_PLACE on a scatter's root -- its block stays
+ * where it is.  A sender that announces more stream bytes than the receiver
+ * has room for is cut at the room.  Size 1 is at most one job on the
+ * caller's stream.  root out of range: MX_ERR_ARG.
+ *
+ * A multi-process call opens with one row exchange through the registration
+ * page (a host wait for every rank, so the call is collective in time):
+ * every rank publishes its significant sides -- layout, span, stream bytes,
+ * access unit, address mod 16, the root's in-place bit, root, kind, a verdict
+ * -- and the root its per-rank blocks.  The ranks need not describe alike:
+ * the root may receive into a vector type from ranks that send bytes.  The
+ * verdict is a function of the rows alone: ranks that disagree on root or
+ * kind all get MX_ERR_ARG; when a rank passes MX_DDT_NONE, a datatype does
+ * not qualify, a word would be below 4 bytes, size x largest block is at or
+ * under mx_comm_set_exchange_min or there is no registration page, every
+ * rank returns MX_ERR_UNSUPPORTED before a byte moves, and the communicator
+ * stays usable.
+ * Data path: from mx_comm_set_reg_min bytes (size x largest block) up, with
+ * the root not in place, a gather's root pulls every block from the peers'
+ * registered send spans in one launch and a scatter's non-roots pull theirs
+ * from the root's; otherwise the blocks go through the staging in rounds --
+ * the slots of the gather's root, the whole staging of each scatter
+ * receiver (mx_comm_rooted_rounds).  Device waits name only the ranks a
+ * kernel depends on. */
+int mx_gather(mx_comm_t *comm, const void *sbuf, size_t scount, const mx_ddt_t *sddt, void *rbuf, size_t rcount,
+              const mx_ddt_t *rddt, int root, void *stream);
+int mx_gatherv(mx_comm_t *comm, const void *sbuf, size_t scount, const mx_ddt_t *sddt, void *rbuf,
+               const size_t *rcounts, const int64_t *rdispls, const mx_ddt_t *rddt, int root, void *stream);
+int mx_scatter(mx_comm_t *comm, const void *sbuf, size_t scount, const mx_ddt_t *sddt, void *rbuf, size_t rcount,
+               const mx_ddt_t *rddt, int root, void *stream);
+int mx_scatterv(mx_comm_t *comm, const void *sbuf, const size_t *scounts, const int64_t *sdispls,
+                const mx_ddt_t *sddt, void *rbuf, size_t rcount, const mx_ddt_t *rddt, int root, void *stream);
+/* out: [0] calls of the four above and their _local forms, [1] zero-copy
+ * calls, [2] staged calls, [3] staged rounds; the exchange counters do not
+ * move for them.  comm NULL: the sums over this process's communicators. */
+int mx_comm_rooted_stats(mx_comm_t *comm, uint64_t out[4]);
+/* the staging rounds a staged gather (scatter = 0) or scatter whose largest
+ * block is max_block bytes takes (0 on a local communicator) */
+long long mx_comm_rooted_rounds(const mx_comm_t *comm, int scatter, size_t max_block);
+
 /* Rooted reduce (coll slot `reduce`, coll.h:239-241): the result lands in
  * rbuf on `root` only (rbuf may be NULL elsewhere); sbuf MPI_IN_PLACE on
  * the root.  Bit-identical to the reference algorithm `alg` (the tree of
@@ -652,6 +708,21 @@ int mx_alltoall_ddt_local(mx_comm_t *comm, const void *const *sbufs, size_t scou
 int mx_alltoallv_ddt_local(mx_comm_t *comm, const void *const *sbufs, const size_t *scounts, const int64_t *sdispls,
                            const mx_ddt_t *sddt, void *const *rbufs, const size_t *rcounts, const int64_t *rdispls,
                            const mx_ddt_t *rddt, void *stream);
+/* The rooted forms on a local communicator, one launch per MX_MAX_RANKS
+ * jobs: sbufs / rbufs hold `size` buffers, every rank uses sddt / rddt.
+ * Only rbufs[root] (gathers) or sbufs[root] (scatters) is read on the many-
+ * block side; the v-forms take one count per rank on the other side.
+ * sbufs[root] (gathers) or rbufs[root] (scatters) MX_IN_PLACE: in place. */
+int mx_gather_local(mx_comm_t *comm, const void *const *sbufs, size_t scount, const mx_ddt_t *sddt,
+                    void *const *rbufs, size_t rcount, const mx_ddt_t *rddt, int root, void *stream);
+int mx_gatherv_local(mx_comm_t *comm, const void *const *sbufs, const size_t *scounts, const mx_ddt_t *sddt,
+                     void *const *rbufs, const size_t *rcounts, const int64_t *rdispls, const mx_ddt_t *rddt,
+                     int root, void *stream);
+int mx_scatter_local(mx_comm_t *comm, const void *const *sbufs, size_t scount, const mx_ddt_t *sddt,
+                     void *const *rbufs, size_t rcount, const mx_ddt_t *rddt, int root, void *stream);
+int mx_scatterv_local(mx_comm_t *comm, const void *const *sbufs, const size_t *scounts, const int64_t *sdispls,
+                      const mx_ddt_t *sddt, void *const *rbufs, const size_t *rcounts, const mx_ddt_t *rddt,
+                      int root, void *stream);
 int mx_reduce_local(mx_comm_t *comm, const void *const *sbufs, void *const *rbufs, size_t count,
                     int type, int op, int root, int alg, void *stream);
 int mx_scan_local(mx_comm_t *comm, const void *const *sbufs, void *const *rbufs, size_t count,

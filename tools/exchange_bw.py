@@ -131,11 +131,85 @@ def ddt_leg(out):
             f.write(text)
 
 
+def rooted_leg(out):
+    import torch
+    import mxompi
+    mxompi.init(0)
+    comm = mxompi.Comm.local(N)
+    st = torch.cuda.current_stream().cuda_stream
+    # (name, the ranks' side, the root's side): flat, and the three shapes of --ddt
+    shapes = [("flat", None, None),
+              ("W16 blen 64/stride 128", _vector(16, 8, 4, 128), _vector(16, 8, 4, 128)),
+              ("W8  blen 8/stride 16", _vector(8, 64, 1, 16), _vector(8, 64, 1, 16)),
+              ("W4  blen 4/stride 8 -> flat", _vector(4, 128, 1, 8), None)]
+    lines = [f"# exchange_bw --rooted: local communicator, n = {N}, root 0, {torch.cuda.get_device_name(0)}",
+             "# a gather / scatter moves n blocks; (k) allgather_local of block/n bytes per rank moves the same n x block",
+             "# bytes through k_copy; (a) the alltoall of the same shape moves n x n blocks",
+             "# GB/s = 2 x payload / median call time (host clock, blocking calls); vs (k), vs (a): ratios of GB/s",
+             f"{'block':>10} {'shape':<28} {'case':<26} {'payload MiB':>12} {'us':>10} {'GB/s':>9} {'vs (k)':>7} {'vs (a)':>7}"]
+    for S in (4 << 10, 32 << 10, 256 << 10, 2 << 20, 16 << 20, 32 << 20):
+        for name, one, many in shapes:
+            # W4: the strided side sends (the ranks of a gather, the root of a scatter), the flat side receives
+            c1 = S // one.size if one else S
+            cm = S // many.size if many else S
+            span1 = c1 * (one.extent if one else 1)
+            spanm = N * cm * (many.extent if many else 1)
+            tr = name.startswith("W4")
+            sing = [torch.empty(span1 + 64, dtype=torch.uint8, device="cuda").random_(0, 256) for _ in range(N)]
+            mult = [torch.empty((N * span1 if tr else spanm) + 64, dtype=torch.uint8, device="cuda").random_(0, 256)]
+            flatm = [torch.empty(N * S + 64, dtype=torch.uint8, device="cuda").zero_()]
+            flat1 = [torch.empty(S + 64, dtype=torch.uint8, device="cuda").zero_() for _ in range(N)]
+            a2a_s = [torch.empty(spanm if many else N * span1 + 64, dtype=torch.uint8, device="cuda") for _ in range(N)]
+            a2a_r = [torch.empty(spanm + 64 if many else N * S + 64, dtype=torch.uint8, device="cuda") for _ in range(N)]
+            kc_s = [torch.empty(S // N, dtype=torch.uint8, device="cuda") for _ in range(N)]
+            kc_r = [torch.empty(S, dtype=torch.uint8, device="cuda") for _ in range(N)]
+            P = lambda ts: mxompi._ptrs([t.data_ptr() for t in ts])   # noqa: E731
+            rest = [0] * (N - 1)
+            sp, fp1, kp, kq, ap, aq = P(sing), P(flat1), P(kc_s), P(kc_r), P(a2a_s), P(a2a_r)
+            mp, fpm = mxompi._ptrs([mult[0].data_ptr()] + rest), mxompi._ptrs([flatm[0].data_ptr()] + rest)
+            if tr:
+                # gather: strided ranks -> flat root; scatter: strided root (n blocks of the ranks' type) -> flat ranks
+                g = lambda: comm.gather_local(sp, c1, one, fpm, S, None, 0, st)          # noqa: E731
+                s = lambda: comm.scatter_local(mp, c1, one, fp1, S, None, 0, st)         # noqa: E731
+                a = lambda: comm.alltoall_ddt_local(ap, c1, one, aq, S, None, st)        # noqa: E731
+            elif one is None:
+                g = lambda: comm.gather_local(sp, S, None, fpm, S, None, 0, st)          # noqa: E731
+                s = lambda: comm.scatter_local(fpm, S, None, sp, S, None, 0, st)         # noqa: E731
+                a = lambda: comm.alltoall_local(ap, aq, S, st)                           # noqa: E731
+            else:
+                g = lambda: comm.gather_local(sp, c1, one, mp, cm, many, 0, st)          # noqa: E731
+                s = lambda: comm.scatter_local(mp, cm, many, sp, c1, one, 0, st)         # noqa: E731
+                a = lambda: comm.alltoall_ddt_local(ap, cm, many, aq, cm, many, st)      # noqa: E731
+            k = lambda: comm.allgather_local(kp, kq, S // N, st)                         # noqa: E731
+            res = {}
+            for case, fn, payload in (("(k) allgather_local (k_copy)", k, N * S), ("(a) alltoall, same shape", a, N * N * S),
+                                      ("(g) gather_local", g, N * S), ("(s) scatter_local", s, N * S)):
+                t, gbs = _time(fn, payload)
+                res[case[:3]] = gbs
+                lines.append(f"{S:>10} {name:<28} {case:<26} {payload / 2**20:>12.2f} {t * 1e6:>10.1f} {gbs:>9.1f} "
+                             f"{gbs / res['(k)']:>7.2f} {gbs / res.get('(a)', gbs):>7.2f}")
+            del sing, mult, flatm, flat1, a2a_s, a2a_r, kc_s, kc_r
+            torch.cuda.empty_cache()
+    comm.close()
+    text = "\n".join(lines) + "\n"
+    print(text, end="")
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--ddt", action="store_true", help="time the strided exchange against its composition")
+    ap.add_argument("--rooted", action="store_true", help="time gather and scatter beside k_copy and the alltoall")
     args = ap.parse_args()
+    if args.rooted:
+        import torch
+        if not torch.cuda.is_available():
+            sys.exit("exchange_bw: no GPU")
+        return rooted_leg(args.out)
     if args.ddt:
         import torch
         if not torch.cuda.is_available():

@@ -55,6 +55,7 @@
 #include "../../include/mx_convertor.h"
 #include "mx_env.hpp"
 #include "mx_exchange.hpp"
+#include "mx_rooted_plan.hpp"
 
 namespace mx {
 
@@ -366,10 +367,12 @@ struct XRowExt {
   int64_t lo;
   uint32_t sunit, runit;
   int32_t verdict, pad;
+  RRowHead r;   // the rooted forms (mx_gather ...): bytes[] / offs[] then carry the root's per-rank blocks
 };
 struct XRow {
   std::atomic<uint64_t> seq;
-  uint64_t flags;   // bits 0-3: the send buffer's address mod 16; bit 4: the rank calls in place; bit 5: a strided form
+  uint64_t flags;   // bits 0-3: the send buffer's address mod 16; bit 4: the rank calls in place; bit 5: a strided form;
+                    // bit 6: a rooted form
   uint64_t bytes[MAXR], offs[MAXR];
   XRowExt e;
 };
@@ -409,6 +412,13 @@ static std::atomic<uint64_t> g_xst[4], g_xdst[4];   // byte forms, strided forms
 static void xcount(mx_comm *c, int k, bool ddt = false) {
   (ddt ? c->xdst : c->xst)[k]++;
   (ddt ? g_xdst : g_xst)[k].fetch_add(1, std::memory_order_relaxed);
+}
+
+// the rooted forms' counters (mx_comm_rooted_stats), kept apart from both
+static std::atomic<uint64_t> g_rst[4];
+static void rcount(mx_comm *c, int k) {
+  c->rst[k]++;
+  g_rst[k].fetch_add(1, std::memory_order_relaxed);
 }
 
 static void live_add(mx_comm *c) {
@@ -1634,6 +1644,16 @@ static int signal_wait_all(mx_comm *c, int kind, uint64_t svalue, uint64_t wvalu
   return mx_check_launch();
 }
 
+// signal_all(kind, value), then a wait for the same value from the ranks in `mask` only
+static int signal_wait_mask(mx_comm *c, int kind, uint64_t value, uint32_t mask, hipStream_t s) {
+  if (!mask) return signal_all(c, kind, value, s);
+  SignalArgs a = signal_args(c, kind * MAXR, value);
+  a.poison = c->poison;
+  hipLaunchKernelGGL(k_signal_wait, dim3(kWaitBlocks), dim3(64), 0, s, a, (const uint64_t *)(c->flagmem + kind * MAXR),
+                     mask & ~(1u << c->rank), value, c->timeout_ticks, c->err_dev, c->poison);
+  return mx_check_launch();
+}
+
 static int wait_mask(mx_comm *c, int kind, uint32_t mask, uint64_t value, hipStream_t s) {
   hipLaunchKernelGGL(k_wait, dim3(kWaitBlocks), dim3(64), 0, s, (const uint64_t *)(c->flagmem + kind * MAXR), mask, value,
                      c->timeout_ticks, c->err_dev, c->poison);
@@ -2856,6 +2876,324 @@ extern "C" int mx_alltoall_ddt(mx_comm_t *c, const void *sbuf, size_t scount, co
     rd[p] = (int64_t)p * (int64_t)rcount;
   }
   return mx_alltoallv_ddt(c, sbuf ? sbuf : MX_IN_PLACE, sc, sd, sddt, rbuf, rc, rd, rddt, stream);
+}
+
+// ---------------------------------------------------------------------------
+// rooted exchanges: gather, gatherv, scatter, scatterv.  Every decision --
+// who launches which jobs, which flags a kernel waits for, how the staging
+// is cut -- is planned on the host (mx_rooted_plan.hpp); here the plan's
+// jobs are resolved to pointers and handed to the two exchange kernels
+// between the flag kernels.  A rank knows only its own sides: the rows of
+// the registration page carry what the others need, and the verdict is a
+// function of the rows alone.
+// ---------------------------------------------------------------------------
+namespace {
+
+struct RBufs {                  // what a job's ends resolve to in this process
+  const char *single[MAXR];     // rank p's single-side user pointer (a peer's: where its span is mapped)
+  const char *multi;            // the root's multi-side user pointer
+  char *stage[MAXR];
+};
+
+static int rooted_launch(mx_comm *c, const RBufs &b, const std::vector<RJob> &jobs, hipStream_t s) {
+  XJob bj[MAXR];
+  XVJob vj[MAXR];
+  int nb = 0, nv = 0;
+  auto end_ptr = [&](const REnd &e) {
+    const char *base = e.buf == RB_SINGLE ? b.single[e.rank] : e.buf == RB_MULTI ? b.multi : b.stage[e.rank];
+    return padd(base, (uint64_t)e.off);
+  };
+  for (const RJob &j : jobs) {
+    if (nb >= MAXR || nv >= MAXR) return MX_ERR_ARG;
+    const char *src = end_ptr(j.s);
+    char *dst = end_ptr(j.d);
+    if (j.bytes) {   // flat -> flat: any length, any alignment
+      bj[nb++] = XJob{padd(src, (uint64_t)xlay_off(j.s.lay, j.s.pos)), padd(dst, (uint64_t)xlay_off(j.d.lay, j.d.pos)),
+                      (size_t)j.len};
+    } else if (int rc = xvjob_make(src, j.s.lay, j.s.pos, dst, j.d.lay, j.d.pos, j.len, &vj[nv++])) {
+      return rc;
+    }
+  }
+  if (nb)
+    if (int rc = exchange_launch(bj, (size_t)nb, c->poison, s)) return rc;
+  return nv ? exchange_vec_launch(vj, (size_t)nv, c->poison, s) : MX_SUCCESS;
+}
+
+// One rank's arguments: its single side (what it sends to a gather, where
+// it receives from a scatter) and, on the root, the multi side.
+struct RArgs {
+  const void *single;
+  size_t count;
+  const mx_ddt_t *ddt;
+  const void *multi;
+  const size_t *counts;
+  const int64_t *displs;
+  const mx_ddt_t *mddt;
+  bool inplace;   // the root only
+};
+
+// the row `rank` publishes; span / mspan: the bytes from lo / mlo it would register
+static int rooted_row(int n, int rank, int kind, int root, const RArgs &a, RRow *row, size_t *span, size_t *mspan) {
+  memset(row, 0, sizeof *row);
+  RRowHead &h = row->h;
+  h.root = root;
+  h.kind = kind;
+  h.verdict = 1;
+  h.lay = h.mlay = xlay_flat();
+  h.unit = h.munit = 16;
+  *span = *mspan = 0;
+  const bool is_root = rank == root;
+  h.inplace = is_root && a.inplace;
+  if (!h.inplace) {
+    const XDSide S = xd_side(a.ddt, kind == RK_SCATTER);
+    if (!S.ok) {
+      h.verdict = 0;
+    } else {
+      if (!xd_counts_ok(S, 1, &a.count)) return MX_ERR_ARG;
+      h.bytes = a.count * S.size;
+      if (h.bytes && !a.single) return MX_ERR_ARG;
+      h.lay = S.lay;
+      int64_t lo = INT64_MAX, hi = INT64_MIN;
+      xd_span(S, a.count, 0, &lo, &hi);
+      if (lo > hi) lo = hi = 0;
+      h.lo = lo;
+      *span = (size_t)(hi - lo);
+      if (h.bytes) h.unit = xlay_unit(S.lay, (uintptr_t)a.single);
+      h.mis = (uint32_t)(((uintptr_t)a.single + (uint64_t)S.lay.disp) & 15);
+    }
+  }
+  if (!is_root) return MX_SUCCESS;
+  const XDSide M = xd_side(a.mddt, kind == RK_GATHER);
+  if (!M.ok) {
+    h.verdict = 0;
+    return MX_SUCCESS;
+  }
+  if (!a.counts || !a.displs || !xd_counts_ok(M, n, a.counts)) return MX_ERR_ARG;
+  int64_t lo = INT64_MAX, hi = INT64_MIN;
+  uint64_t total = 0;
+  for (int p = 0; p < n; p++) {
+    row->mbytes[p] = a.counts[p] * M.size;
+    row->moffs[p] = a.displs[p] * M.ext;
+    if (p != root || !h.inplace) total += row->mbytes[p];
+    xd_span(M, a.counts[p], a.displs[p], &lo, &hi);
+  }
+  if (total && !a.multi) return MX_ERR_ARG;
+  if (lo > hi) lo = hi = 0;
+  h.mlay = M.lay;
+  h.mlo = lo;
+  *mspan = (size_t)(hi - lo);
+  if (total) h.munit = xlay_unit(M.lay, (uintptr_t)a.multi);
+  h.mmis = (uint32_t)(((uintptr_t)a.multi + (uint64_t)M.lay.disp) & 15);
+  return MX_SUCCESS;
+}
+
+// a communicator of one process (and a communicator of one rank): every
+// block in one launch per kernel, planned before anything is launched
+static int rooted_local(mx_comm *c, int kind, int root, const RArgs *args, hipStream_t s) {
+  const int n = c->size;
+  std::vector<RRow> rows((size_t)n);
+  size_t span, mspan;
+  for (int p = 0; p < n; p++)
+    if (int rc = rooted_row(n, p, kind, root, args[p], &rows[(size_t)p], &span, &mspan)) return rc;
+  RHead h;
+  if (int rc = rooted_verdict(rows.data(), n, 0, &h)) return rc;
+  if (int orc = order(c, s)) return orc;
+  rcount(c, 0);
+  RBufs b;
+  memset(&b, 0, sizeof b);
+  for (int p = 0; p < n; p++) b.single[p] = (const char *)args[p].single;
+  b.multi = (const char *)args[root].multi;
+  std::vector<RJob> jobs;
+  rooted_local_jobs(h, rows.data(), jobs);
+  if (int rc = rooted_launch(c, b, jobs, s)) return rc;
+  return finish(c, s);
+}
+
+static int rooted_mp(mx_comm *c, int kind, int root, const RArgs &a, hipStream_t s) {
+  const int n = c->size, r = c->rank;
+  RRow all[MAXR];
+  size_t span, mspan;
+  if (int rc = rooted_row(n, r, kind, root, a, &all[r], &span, &mspan)) return rc;
+  if (!c->reg_shm) return MX_ERR_UNSUPPORTED;   // agreed at creation: every rank returns here
+  XRowExt e;
+  memset(&e, 0, sizeof e);
+  e.r = all[r].h;
+  e.verdict = all[r].h.verdict;
+  const XRow *rows = nullptr;
+  if (int rc = xrow_exchange(c, (const size_t *)all[r].mbytes, (const size_t *)all[r].moffs, 64, &rows, &e)) return rc;
+  for (int p = 0; p < n; p++) {
+    if (!(rows[p].flags & 64)) return MX_ERR_ARG;   // another collective on some rank: every rank sees it
+    all[p].h = rows[p].e.r;
+    for (int q = 0; q < n; q++) {
+      all[p].mbytes[q] = rows[p].bytes[q];
+      all[p].moffs[q] = (int64_t)rows[p].offs[q];
+    }
+  }
+  RHead h;
+  if (int rc = rooted_verdict(all, n, c->xmin, &h)) return rc;   // the same on every rank, before any byte moves
+  DoneMark dm;
+  done_mark_arm(c, dm);
+  rcount(c, 0);
+  if (!h.max_block) return MX_SUCCESS;   // nothing moves on any rank
+  RBufs b;
+  memset(&b, 0, sizeof b);
+  b.single[r] = (const char *)a.single;
+  b.multi = (const char *)a.multi;
+  for (int p = 0; p < n; p++) b.stage[p] = c->peer_staging[p];
+  std::vector<RJob> jobs;
+  int rc;
+  if (!h.inplace && zc_allowed(c, ZC_DEFAULT, (size_t)n * (size_t)h.max_block)) {
+    // zero-copy: the gather's root pulls every block from the peers'
+    // registered send spans; a scatter's non-root pulls its block from the
+    // root's.  A rank registers its single side, the root its multi side too.
+    const char *ps[MAXR];
+    char *pr[MAXR];
+    const char *A = padd((const char *)a.single, (uint64_t)all[r].h.lo);
+    const char *B = r == root ? padd((const char *)a.multi, (uint64_t)all[r].h.mlo) : A;
+    const size_t bspan = r == root ? mspan : span;
+    const int zc = reg_exchange(c, A, span, (char *)B, bspan, 0, span && bspan, ps, pr);
+    if (zc < 0) return zc;
+    if (zc) {
+      const uint64_t g = ++c->gen;
+      rcount(c, 1);
+      for (int p = 0; p < n; p++)
+        if (p != r) b.single[p] = padd(ps[p], (uint64_t)0 - (uint64_t)all[p].h.lo);
+      if (r != root) b.multi = padd(pr[root], (uint64_t)0 - (uint64_t)all[root].h.mlo);
+      if ((rc = signal_wait_mask(c, FLAG_READY, g << 1, rooted_zc_ready_mask(h, r), s))) return rc;   // the source holds its block
+      rooted_zc_jobs(h, all, r, jobs);
+      if ((rc = rooted_launch(c, b, jobs, s))) return rc;
+      if ((rc = signal_wait_mask(c, FLAG_PUSHED, g, rooted_zc_pushed_mask(h, r), s))) return rc;   // my buffer's readers are done
+      if ((rc = signal_done(c, g, s, &dm))) return rc;
+      return finish_done(c, s, dm);
+    }
+  }
+  RGeom geo;
+  if (!rooted_geom(c->main_bytes, n, kind, h.max_block, &geo)) return MX_ERR_NOMEM;
+  rcount(c, 2);
+  for (uint64_t q = 0; q < geo.rounds; q++) {
+    const uint64_t g = ++c->gen;
+    rcount(c, 3);
+    // The stagings this rank writes must be free.  Between the rounds of this
+    // call only their owners read them: the owners' DONE(g - 1).  Before the
+    // first round the generation before was another collective's, in which
+    // any rank may have read a peer's staging (the PULL allreduce folds from
+    // it), so there a writer waits for every rank's DONE(g - 1).
+    if (uint32_t dmask = rooted_staged_done_mask(h, geo, r, q)) {
+      if (q == 0) dmask = all_ranks_mask(n) & ~(1u << r);
+      if ((rc = wait_mask(c, FLAG_DONE, dmask, g - 1, s))) return rc;
+    }
+    rooted_staged_jobs(h, all, geo, r, q, 0, jobs);
+    if ((rc = rooted_launch(c, b, jobs, s))) return rc;
+    if ((rc = signal_wait_mask(c, FLAG_READY, g << 1, rooted_staged_ready_mask(h, geo, r, q), s))) return rc;
+    rooted_staged_jobs(h, all, geo, r, q, 1, jobs);
+    if ((rc = rooted_launch(c, b, jobs, s))) return rc;
+    if ((rc = signal_done(c, g, s, q + 1 == geo.rounds ? &dm : nullptr))) return rc;
+  }
+  return finish_done(c, s, dm);
+}
+
+static int rooted_call(mx_comm *c, int kind, int root, const RArgs &a, void *stream) {
+  if (!c || (c->local && c->size != 1)) return c && c->local ? MX_ERR_STATE : MX_ERR_ARG;
+  if (root < 0 || root >= c->size) return MX_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  if (c->size == 1) return rooted_local(c, kind, root, &a, s);   // at most one job on the caller's stream
+  if (int rc = exchange_enter(c, s)) return rc;
+  return rooted_mp(c, kind, root, a, s);
+}
+
+// the blocks of gather / scatter in the multi side: rank p's at p x count
+struct REven {
+  size_t counts[MAXR];
+  int64_t displs[MAXR];
+  REven(int n, size_t count) {
+    for (int p = 0; p < MAXR; p++) {
+      counts[p] = p < n ? count : 0;
+      displs[p] = (int64_t)p * (int64_t)count;
+    }
+  }
+};
+
+static int rooted_local_call(mx_comm_t *c, int kind, const void *const *singles, const size_t *counts1,
+                             const mx_ddt_t *ddt, const void *const *multis, const size_t *counts,
+                             const int64_t *displs, const mx_ddt_t *mddt, int root, void *stream) {
+  if (!c || !c->local) return MX_ERR_ARG;
+  if (root < 0 || root >= c->size || !singles || !multis || !counts1) return MX_ERR_ARG;
+  RArgs args[MAXR];
+  for (int p = 0; p < c->size; p++) {
+    const bool inplace = p == root && singles[p] == MX_IN_PLACE;
+    args[p] = RArgs{singles[p], counts1[p], ddt, p == root ? multis[p] : nullptr, counts, displs, mddt, inplace};
+  }
+  return rooted_local(c, kind, root, args, (hipStream_t)stream);
+}
+
+}  // namespace
+
+extern "C" int mx_gatherv(mx_comm_t *c, const void *sbuf, size_t scount, const mx_ddt_t *sddt, void *rbuf,
+                          const size_t *rcounts, const int64_t *rdispls, const mx_ddt_t *rddt, int root,
+                          void *stream) {
+  const bool is_root = c && c->rank == root;
+  return rooted_call(c, RK_GATHER, root,
+                     RArgs{sbuf, scount, sddt, rbuf, rcounts, rdispls, rddt, is_root && sbuf == MX_IN_PLACE}, stream);
+}
+
+extern "C" int mx_gather(mx_comm_t *c, const void *sbuf, size_t scount, const mx_ddt_t *sddt, void *rbuf,
+                         size_t rcount, const mx_ddt_t *rddt, int root, void *stream) {
+  const REven ev(c ? c->size : 0, rcount);
+  return mx_gatherv(c, sbuf, scount, sddt, rbuf, ev.counts, ev.displs, rddt, root, stream);
+}
+
+extern "C" int mx_scatterv(mx_comm_t *c, const void *sbuf, const size_t *scounts, const int64_t *sdispls,
+                           const mx_ddt_t *sddt, void *rbuf, size_t rcount, const mx_ddt_t *rddt, int root,
+                           void *stream) {
+  const bool is_root = c && c->rank == root;
+  return rooted_call(c, RK_SCATTER, root,
+                     RArgs{rbuf, rcount, rddt, sbuf, scounts, sdispls, sddt, is_root && rbuf == MX_IN_PLACE}, stream);
+}
+
+extern "C" int mx_scatter(mx_comm_t *c, const void *sbuf, size_t scount, const mx_ddt_t *sddt, void *rbuf,
+                          size_t rcount, const mx_ddt_t *rddt, int root, void *stream) {
+  const REven ev(c ? c->size : 0, scount);
+  return mx_scatterv(c, sbuf, ev.counts, ev.displs, sddt, rbuf, rcount, rddt, root, stream);
+}
+
+extern "C" int mx_gatherv_local(mx_comm_t *c, const void *const *sbufs, const size_t *scounts, const mx_ddt_t *sddt,
+                                void *const *rbufs, const size_t *rcounts, const int64_t *rdispls,
+                                const mx_ddt_t *rddt, int root, void *stream) {
+  return rooted_local_call(c, RK_GATHER, sbufs, scounts, sddt, (const void *const *)rbufs, rcounts, rdispls, rddt, root,
+                           stream);
+}
+
+extern "C" int mx_gather_local(mx_comm_t *c, const void *const *sbufs, size_t scount, const mx_ddt_t *sddt,
+                               void *const *rbufs, size_t rcount, const mx_ddt_t *rddt, int root, void *stream) {
+  const REven one(c ? c->size : 0, scount), ev(c ? c->size : 0, rcount);
+  return mx_gatherv_local(c, sbufs, one.counts, sddt, rbufs, ev.counts, ev.displs, rddt, root, stream);
+}
+
+extern "C" int mx_scatterv_local(mx_comm_t *c, const void *const *sbufs, const size_t *scounts,
+                                 const int64_t *sdispls, const mx_ddt_t *sddt, void *const *rbufs,
+                                 const size_t *rcounts, const mx_ddt_t *rddt, int root, void *stream) {
+  return rooted_local_call(c, RK_SCATTER, (const void *const *)rbufs, rcounts, rddt, sbufs, scounts, sdispls, sddt, root,
+                           stream);
+}
+
+extern "C" int mx_scatter_local(mx_comm_t *c, const void *const *sbufs, size_t scount, const mx_ddt_t *sddt,
+                                void *const *rbufs, size_t rcount, const mx_ddt_t *rddt, int root, void *stream) {
+  const REven ev(c ? c->size : 0, scount), one(c ? c->size : 0, rcount);
+  return mx_scatterv_local(c, sbufs, ev.counts, ev.displs, sddt, rbufs, one.counts, rddt, root, stream);
+}
+
+extern "C" int mx_comm_rooted_stats(mx_comm_t *c, uint64_t out[4]) {
+  if (!out) return MX_ERR_ARG;
+  for (int k = 0; k < 4; k++) out[k] = c ? c->rst[k] : g_rst[k].load(std::memory_order_relaxed);
+  return MX_SUCCESS;
+}
+
+extern "C" long long mx_comm_rooted_rounds(const mx_comm_t *c, int scatter, size_t max_block) {
+  if (!c) return MX_ERR_ARG;
+  if (c->local || c->size < 2) return 0;
+  RGeom geo;
+  if (!rooted_geom(c->main_bytes, c->size, scatter ? RK_SCATTER : RK_GATHER, max_block, &geo)) return MX_ERR_NOMEM;
+  return (long long)geo.rounds;
 }
 
 // MPI_Bcast, all-peer scatter + allgather (the reference's large-message

@@ -260,6 +260,7 @@ struct mx_comm {
   mx_coll_stats_t st;
   uint64_t xst[4];   // exchanges (mx_comm_exchange_stats): calls, zero-copy calls, staged calls, staged rounds
   uint64_t xdst[4];  // the same four for the strided forms (mx_comm_exchange_ddt_stats)
+  uint64_t rst[4];   // the rooted forms (mx_comm_rooted_stats): the same four
   size_t xmin;       // alltoallv: calls of size x largest pair <= xmin are declined (mx_comm_set_exchange_min)
   mx::XTable *xtab;  // table memory of the local forms' n x n launches (mx_exchange.hpp), made on first use
   uint64_t xrow_seq; // alltoallv row exchanges so far (the registration page's row area)

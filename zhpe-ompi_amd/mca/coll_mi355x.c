@@ -130,6 +130,14 @@ typedef struct {
     mca_coll_base_module_t *prev_alltoallv_module;
     mca_coll_base_module_allgatherv_fn_t prev_allgatherv;
     mca_coll_base_module_t *prev_allgatherv_module;
+    mca_coll_base_module_gather_fn_t prev_gather;
+    mca_coll_base_module_t *prev_gather_module;
+    mca_coll_base_module_gatherv_fn_t prev_gatherv;
+    mca_coll_base_module_t *prev_gatherv_module;
+    mca_coll_base_module_scatter_fn_t prev_scatter;
+    mca_coll_base_module_t *prev_scatter_module;
+    mca_coll_base_module_scatterv_fn_t prev_scatterv;
+    mca_coll_base_module_t *prev_scatterv_module;
     mca_coll_base_module_reduce_local_fn_t prev_reduce_local;
     mca_coll_base_module_t *prev_reduce_local_module;
     mca_coll_base_module_reduce_fn_t prev_reduce;
@@ -204,6 +212,10 @@ static void coll_module_destruct(mx_coll_module_t *m)
     if (m->prev_alltoall_module) MX_OBJ_RELEASE(m->prev_alltoall_module);
     if (m->prev_alltoallv_module) MX_OBJ_RELEASE(m->prev_alltoallv_module);
     if (m->prev_allgatherv_module) MX_OBJ_RELEASE(m->prev_allgatherv_module);
+    if (m->prev_gather_module) MX_OBJ_RELEASE(m->prev_gather_module);
+    if (m->prev_gatherv_module) MX_OBJ_RELEASE(m->prev_gatherv_module);
+    if (m->prev_scatter_module) MX_OBJ_RELEASE(m->prev_scatter_module);
+    if (m->prev_scatterv_module) MX_OBJ_RELEASE(m->prev_scatterv_module);
     if (m->prev_reduce_local_module) MX_OBJ_RELEASE(m->prev_reduce_local_module);
     if (m->prev_reduce_module) MX_OBJ_RELEASE(m->prev_reduce_module);
     if (m->prev_reduce_scatter_block_module) MX_OBJ_RELEASE(m->prev_reduce_scatter_block_module);
@@ -996,6 +1008,182 @@ static int mx_coll_allgatherv(const void *sbuf, int scount, struct ompi_datatype
     return host_allgatherv(m, sbuf, scount, sdtype, rbuf, rcounts, disps, rdtype);
 }
 
+/* ---- rooted exchanges: gather, gatherv, scatter, scatterv ----------------------
+ * The receive arguments of a gather and the send arguments of a scatter are
+ * significant on the root only, so no rank can judge the other side: a rank
+ * looks at its own arguments alone and the library's row exchange settles the
+ * route for all.  A call enters the library when the communicator has at most
+ * MX_MAX_RANKS ranks and, for gather and scatter, the block -- the rank's own
+ * count x its own type size, which MPI's signature rule makes equal on every
+ * rank; the root of an in-place gather takes its receive count -- is above
+ * coll_mi355x_host_max_kb.  The v-forms have no size every rank shares: they
+ * always enter and the library declines after the row exchange.  A rank whose
+ * significant buffer is host memory, or whose datatype the host cannot
+ * describe, passes MX_DDT_NONE: it still takes part, every rank gets
+ * MX_ERR_UNSUPPORTED, and every rank runs the saved module through host
+ * views.  The views are copied in, so the bytes between the blocks come back
+ * unchanged.  Contiguous and derived datatypes take the same entry points
+ * (counts stay instances). */
+static const mx_ddt_t *rooted_ddt(mx_coll_module_t *m, const void *buf, int moves, struct ompi_datatype_t *dt)
+{
+    if (moves && mx_is_device_ptr(buf) != 1) return MX_DDT_NONE;
+    return xch_ddt(m, dt);
+}
+static void rooted_tables(int n, const int *counts, const int *displs, size_t *c, int64_t *d)
+{
+    for (int i = 0; i < n; i++) {
+        c[i] = counts[i] > 0 ? (size_t)counts[i] : 0;
+        d[i] = displs[i];
+    }
+}
+
+static int host_gather(mx_coll_module_t *m, const void *sbuf, int scount, struct ompi_datatype_t *sdtype, void *rbuf,
+                       int rcount, struct ompi_datatype_t *rdtype, int root)
+{
+    const int n = mx_ompi_host->comm_size(m->comm), is_root = mx_ompi_host->comm_rank(m->comm) == root;
+    hview_t s, r;
+    void *hs, *hr = rbuf;
+    memset(&r, 0, sizeof r);
+    int rc = sbuf == MPI_IN_PLACE ? (hs = (void *)sbuf, MX_SUCCESS) : hview_in(m, SCR_IN, sbuf, sdtype, (size_t)scount, 1, &s, &hs);
+    if (!rc && is_root) rc = hview_in(m, SCR_OUT, rbuf, rdtype, (size_t)rcount * n, 1, &r, &hr);
+    if (rc) return map_rc(rc);
+    int ret = m->prev_gather(hs, scount, sdtype, hr, rcount, rdtype, root, m->comm, m->prev_gather_module);
+    if (ret == OMPI_SUCCESS) ret = map_rc(hview_out(m, &r));
+    return ret;
+}
+
+static int mx_coll_gather(const void *sbuf, int scount, struct ompi_datatype_t *sdtype, void *rbuf, int rcount,
+                          struct ompi_datatype_t *rdtype, int root, struct ompi_communicator_t *comm,
+                          mca_coll_base_module_t *module)
+{
+    mx_coll_module_t *m = (mx_coll_module_t *)module;
+    const int n = mx_ompi_host->comm_size(comm), is_root = mx_ompi_host->comm_rank(comm) == root;
+    const int inplace = is_root && sbuf == MPI_IN_PLACE;
+    const size_t bytes = inplace ? (size_t)rcount * mx_ompi_host->dtype_size(rdtype)
+                                 : (size_t)scount * mx_ompi_host->dtype_size(sdtype);
+    if (n <= MX_MAX_RANKS && big(m, bytes) && comm_ready(m)) {
+        int rc = begin(m);
+        if (!rc)
+            rc = mx_gather(m->mx, inplace ? MX_IN_PLACE : sbuf, inplace ? 0 : (size_t)scount,
+                           inplace ? NULL : rooted_ddt(m, sbuf, 1, sdtype), is_root ? rbuf : NULL,
+                           is_root ? (size_t)rcount : 0, is_root ? rooted_ddt(m, rbuf, 1, rdtype) : NULL, root,
+                           m->stream);
+        if (rc != MX_ERR_UNSUPPORTED) return map_rc(rc);
+    }
+    return host_gather(m, sbuf, scount, sdtype, rbuf, rcount, rdtype, root);
+}
+
+static int host_gatherv(mx_coll_module_t *m, const void *sbuf, int scount, struct ompi_datatype_t *sdtype, void *rbuf,
+                        const int *rcounts, const int *disps, struct ompi_datatype_t *rdtype, int root)
+{
+    const int n = mx_ompi_host->comm_size(m->comm), is_root = mx_ompi_host->comm_rank(m->comm) == root;
+    hview_t s, r;
+    void *hs, *hr = rbuf;
+    memset(&r, 0, sizeof r);
+    int rc = sbuf == MPI_IN_PLACE ? (hs = (void *)sbuf, MX_SUCCESS) : hview_in(m, SCR_IN, sbuf, sdtype, (size_t)scount, 1, &s, &hs);
+    if (!rc && is_root) rc = hview_in(m, SCR_OUT, rbuf, rdtype, xch_span(n, rcounts, disps), 1, &r, &hr);
+    if (rc) return map_rc(rc);
+    int ret = m->prev_gatherv(hs, scount, sdtype, hr, rcounts, disps, rdtype, root, m->comm, m->prev_gatherv_module);
+    if (ret == OMPI_SUCCESS) ret = map_rc(hview_out(m, &r));
+    return ret;
+}
+
+static int mx_coll_gatherv(const void *sbuf, int scount, struct ompi_datatype_t *sdtype, void *rbuf,
+                           const int *rcounts, const int *disps, struct ompi_datatype_t *rdtype, int root,
+                           struct ompi_communicator_t *comm, mca_coll_base_module_t *module)
+{
+    mx_coll_module_t *m = (mx_coll_module_t *)module;
+    const int n = mx_ompi_host->comm_size(comm), is_root = mx_ompi_host->comm_rank(comm) == root;
+    const int inplace = is_root && sbuf == MPI_IN_PLACE;
+    if (n <= MX_MAX_RANKS && comm_ready(m)) {
+        size_t rc_[MX_MAX_RANKS];
+        int64_t rd[MX_MAX_RANKS];
+        if (is_root) rooted_tables(n, rcounts, disps, rc_, rd);
+        int rc = begin(m);
+        if (!rc)
+            rc = mx_gatherv(m->mx, inplace ? MX_IN_PLACE : sbuf, inplace || scount < 0 ? 0 : (size_t)scount,
+                            inplace ? NULL : rooted_ddt(m, sbuf, scount > 0, sdtype), is_root ? rbuf : NULL,
+                            is_root ? rc_ : NULL, is_root ? rd : NULL,
+                            is_root ? rooted_ddt(m, rbuf, xch_any(n, rcounts), rdtype) : NULL, root, m->stream);
+        if (rc != MX_ERR_UNSUPPORTED) return map_rc(rc);
+    }
+    return host_gatherv(m, sbuf, scount, sdtype, rbuf, rcounts, disps, rdtype, root);
+}
+
+static int host_scatter(mx_coll_module_t *m, const void *sbuf, int scount, struct ompi_datatype_t *sdtype, void *rbuf,
+                        int rcount, struct ompi_datatype_t *rdtype, int root)
+{
+    const int n = mx_ompi_host->comm_size(m->comm), is_root = mx_ompi_host->comm_rank(m->comm) == root;
+    hview_t s, r;
+    void *hs = (void *)sbuf, *hr = rbuf;
+    memset(&r, 0, sizeof r);
+    int rc = is_root ? hview_in(m, SCR_IN, sbuf, sdtype, (size_t)scount * n, 1, &s, &hs) : MX_SUCCESS;
+    if (!rc && rbuf != MPI_IN_PLACE) rc = hview_in(m, SCR_OUT, rbuf, rdtype, (size_t)rcount, 1, &r, &hr);
+    if (rc) return map_rc(rc);
+    int ret = m->prev_scatter(hs, scount, sdtype, hr, rcount, rdtype, root, m->comm, m->prev_scatter_module);
+    if (ret == OMPI_SUCCESS) ret = map_rc(hview_out(m, &r));
+    return ret;
+}
+
+static int mx_coll_scatter(const void *sbuf, int scount, struct ompi_datatype_t *sdtype, void *rbuf, int rcount,
+                           struct ompi_datatype_t *rdtype, int root, struct ompi_communicator_t *comm,
+                           mca_coll_base_module_t *module)
+{
+    mx_coll_module_t *m = (mx_coll_module_t *)module;
+    const int n = mx_ompi_host->comm_size(comm), is_root = mx_ompi_host->comm_rank(comm) == root;
+    const int inplace = is_root && rbuf == MPI_IN_PLACE;
+    const size_t bytes = inplace ? (size_t)scount * mx_ompi_host->dtype_size(sdtype)
+                                 : (size_t)rcount * mx_ompi_host->dtype_size(rdtype);
+    if (n <= MX_MAX_RANKS && big(m, bytes) && comm_ready(m)) {
+        int rc = begin(m);
+        if (!rc)
+            rc = mx_scatter(m->mx, is_root ? sbuf : NULL, is_root ? (size_t)scount : 0,
+                            is_root ? rooted_ddt(m, sbuf, 1, sdtype) : NULL, inplace ? (void *)MX_IN_PLACE : rbuf,
+                            inplace ? 0 : (size_t)rcount, inplace ? NULL : rooted_ddt(m, rbuf, 1, rdtype), root,
+                            m->stream);
+        if (rc != MX_ERR_UNSUPPORTED) return map_rc(rc);
+    }
+    return host_scatter(m, sbuf, scount, sdtype, rbuf, rcount, rdtype, root);
+}
+
+static int host_scatterv(mx_coll_module_t *m, const void *sbuf, const int *scounts, const int *disps,
+                         struct ompi_datatype_t *sdtype, void *rbuf, int rcount, struct ompi_datatype_t *rdtype,
+                         int root)
+{
+    const int n = mx_ompi_host->comm_size(m->comm), is_root = mx_ompi_host->comm_rank(m->comm) == root;
+    hview_t s, r;
+    void *hs = (void *)sbuf, *hr = rbuf;
+    memset(&r, 0, sizeof r);
+    int rc = is_root ? hview_in(m, SCR_IN, sbuf, sdtype, xch_span(n, scounts, disps), 1, &s, &hs) : MX_SUCCESS;
+    if (!rc && rbuf != MPI_IN_PLACE) rc = hview_in(m, SCR_OUT, rbuf, rdtype, (size_t)rcount, 1, &r, &hr);
+    if (rc) return map_rc(rc);
+    int ret = m->prev_scatterv(hs, scounts, disps, sdtype, hr, rcount, rdtype, root, m->comm, m->prev_scatterv_module);
+    if (ret == OMPI_SUCCESS) ret = map_rc(hview_out(m, &r));
+    return ret;
+}
+
+static int mx_coll_scatterv(const void *sbuf, const int *scounts, const int *disps, struct ompi_datatype_t *sdtype,
+                            void *rbuf, int rcount, struct ompi_datatype_t *rdtype, int root,
+                            struct ompi_communicator_t *comm, mca_coll_base_module_t *module)
+{
+    mx_coll_module_t *m = (mx_coll_module_t *)module;
+    const int n = mx_ompi_host->comm_size(comm), is_root = mx_ompi_host->comm_rank(comm) == root;
+    const int inplace = is_root && rbuf == MPI_IN_PLACE;
+    if (n <= MX_MAX_RANKS && comm_ready(m)) {
+        size_t sc[MX_MAX_RANKS];
+        int64_t sd[MX_MAX_RANKS];
+        if (is_root) rooted_tables(n, scounts, disps, sc, sd);
+        int rc = begin(m);
+        if (!rc)
+            rc = mx_scatterv(m->mx, is_root ? sbuf : NULL, is_root ? sc : NULL, is_root ? sd : NULL,
+                             is_root ? rooted_ddt(m, sbuf, xch_any(n, scounts), sdtype) : NULL,
+                             inplace ? (void *)MX_IN_PLACE : rbuf, inplace || rcount < 0 ? 0 : (size_t)rcount,
+                             inplace ? NULL : rooted_ddt(m, rbuf, rcount > 0, rdtype), root, m->stream);
+        if (rc != MX_ERR_UNSUPPORTED) return map_rc(rc);
+    }
+    return host_scatterv(m, sbuf, scounts, disps, sdtype, rbuf, rcount, rdtype, root);
+}
+
 static int mx_coll_bcast(void *buf, int count, struct ompi_datatype_t *dtype, int root,
                          struct ompi_communicator_t *comm, mca_coll_base_module_t *module)
 {
@@ -1211,6 +1399,53 @@ static int mx_self_allgatherv(const void *sbuf, int scount, struct ompi_datatype
         return m->prev_allgatherv(sbuf, scount, sdtype, rbuf, rcounts, disps, rdtype, comm, m->prev_allgatherv_module);
     return map_rc(self_copy(m, sbuf, sdtype, (size_t)scount, (char *)rbuf + self_displ(rdtype, disps[0]), rdtype,
                             (size_t)rcounts[0]));
+}
+
+/* the rooted exchanges on one rank: the root's own block, a no-op in place */
+static int mx_self_gather(const void *sbuf, int scount, struct ompi_datatype_t *sdtype, void *rbuf, int rcount,
+                          struct ompi_datatype_t *rdtype, int root, struct ompi_communicator_t *comm,
+                          mca_coll_base_module_t *module)
+{
+    mx_coll_module_t *m = (mx_coll_module_t *)module;
+    if (sbuf == MPI_IN_PLACE) return OMPI_SUCCESS;
+    if (!self_device(sbuf, rbuf))
+        return m->prev_gather(sbuf, scount, sdtype, rbuf, rcount, rdtype, root, comm, m->prev_gather_module);
+    return map_rc(self_copy(m, sbuf, sdtype, (size_t)scount, rbuf, rdtype, (size_t)rcount));
+}
+
+static int mx_self_gatherv(const void *sbuf, int scount, struct ompi_datatype_t *sdtype, void *rbuf,
+                           const int *rcounts, const int *disps, struct ompi_datatype_t *rdtype, int root,
+                           struct ompi_communicator_t *comm, mca_coll_base_module_t *module)
+{
+    mx_coll_module_t *m = (mx_coll_module_t *)module;
+    if (sbuf == MPI_IN_PLACE) return OMPI_SUCCESS;
+    if (!self_device(sbuf, rbuf))
+        return m->prev_gatherv(sbuf, scount, sdtype, rbuf, rcounts, disps, rdtype, root, comm, m->prev_gatherv_module);
+    return map_rc(self_copy(m, sbuf, sdtype, (size_t)scount, (char *)rbuf + self_displ(rdtype, disps[0]), rdtype,
+                            (size_t)rcounts[0]));
+}
+
+static int mx_self_scatter(const void *sbuf, int scount, struct ompi_datatype_t *sdtype, void *rbuf, int rcount,
+                           struct ompi_datatype_t *rdtype, int root, struct ompi_communicator_t *comm,
+                           mca_coll_base_module_t *module)
+{
+    mx_coll_module_t *m = (mx_coll_module_t *)module;
+    if (rbuf == MPI_IN_PLACE) return OMPI_SUCCESS;
+    if (!self_device(sbuf, rbuf))
+        return m->prev_scatter(sbuf, scount, sdtype, rbuf, rcount, rdtype, root, comm, m->prev_scatter_module);
+    return map_rc(self_copy(m, sbuf, sdtype, (size_t)scount, rbuf, rdtype, (size_t)rcount));
+}
+
+static int mx_self_scatterv(const void *sbuf, const int *scounts, const int *disps, struct ompi_datatype_t *sdtype,
+                            void *rbuf, int rcount, struct ompi_datatype_t *rdtype, int root,
+                            struct ompi_communicator_t *comm, mca_coll_base_module_t *module)
+{
+    mx_coll_module_t *m = (mx_coll_module_t *)module;
+    if (rbuf == MPI_IN_PLACE) return OMPI_SUCCESS;
+    if (!self_device(sbuf, rbuf))
+        return m->prev_scatterv(sbuf, scounts, disps, sdtype, rbuf, rcount, rdtype, root, comm, m->prev_scatterv_module);
+    return map_rc(self_copy(m, (const char *)sbuf + self_displ(sdtype, disps[0]), sdtype, (size_t)scounts[0], rbuf,
+                            rdtype, (size_t)rcount));
 }
 
 static int mx_self_reduce(const void *sbuf, void *rbuf, int count, struct ompi_datatype_t *dtype, struct ompi_op_t *op,
@@ -2092,6 +2327,7 @@ static int mx_coll_module_enable(mca_coll_base_module_t *module, struct ompi_com
         SAVE_PREV_SELF(allreduce) SAVE_PREV_SELF(reduce_scatter) SAVE_PREV_SELF(allgather) SAVE_PREV_SELF(reduce)
         SAVE_PREV_SELF(reduce_scatter_block) SAVE_PREV_SELF(scan)
         SAVE_PREV_SELF(alltoall) SAVE_PREV_SELF(alltoallv) SAVE_PREV_SELF(allgatherv)
+        SAVE_PREV_SELF(gather) SAVE_PREV_SELF(gatherv) SAVE_PREV_SELF(scatter) SAVE_PREV_SELF(scatterv)
 #undef SAVE_PREV_SELF
         if (m->super.coll_reduce_local) SAVE_PREV(m, comm, reduce_local, mca_coll_base_module_reduce_local_fn_t);
         m->mx_state = -1;   /* no peers: no device communicator */
@@ -2109,6 +2345,10 @@ static int mx_coll_module_enable(mca_coll_base_module_t *module, struct ompi_com
         SAVE_PREV(m, comm, alltoall, mca_coll_base_module_alltoall_fn_t);
         SAVE_PREV(m, comm, alltoallv, mca_coll_base_module_alltoallv_fn_t);
         SAVE_PREV(m, comm, allgatherv, mca_coll_base_module_allgatherv_fn_t);
+        SAVE_PREV(m, comm, gather, mca_coll_base_module_gather_fn_t);
+        SAVE_PREV(m, comm, gatherv, mca_coll_base_module_gatherv_fn_t);
+        SAVE_PREV(m, comm, scatter, mca_coll_base_module_scatter_fn_t);
+        SAVE_PREV(m, comm, scatterv, mca_coll_base_module_scatterv_fn_t);
     }
     if (m->super.coll_reduce_local) SAVE_PREV(m, comm, reduce_local, mca_coll_base_module_reduce_local_fn_t);
     /* nonblocking / persistent: take a slot only where a lower module
@@ -2185,6 +2425,10 @@ static mca_coll_base_module_t *mx_coll_component_comm_query(struct ompi_communic
         m->super.coll_alltoall = mx_coll_alltoall;
         m->super.coll_alltoallv = mx_coll_alltoallv;
         m->super.coll_allgatherv = mx_coll_allgatherv;
+        m->super.coll_gather = mx_coll_gather;
+        m->super.coll_gatherv = mx_coll_gatherv;
+        m->super.coll_scatter = mx_coll_scatter;
+        m->super.coll_scatterv = mx_coll_scatterv;
 #define SET_NB(name) m->super.coll_##name = mx_coll_##name;
         MX_NB_SLOTS(SET_NB)
 #undef SET_NB
@@ -2202,6 +2446,10 @@ static mca_coll_base_module_t *mx_coll_component_comm_query(struct ompi_communic
         m->super.coll_alltoall = mx_self_alltoall;
         m->super.coll_alltoallv = mx_self_alltoallv;
         m->super.coll_allgatherv = mx_self_allgatherv;
+        m->super.coll_gather = mx_self_gather;
+        m->super.coll_gatherv = mx_self_gatherv;
+        m->super.coll_scatter = mx_self_scatter;
+        m->super.coll_scatterv = mx_self_scatterv;
     }
     if (*priority > 75) m->super.coll_reduce_local = mx_coll_reduce_local;
     return &m->super;

@@ -352,7 +352,7 @@ static int mca_int(const char *name, int def)
 }
 
 /* ---- communicators --------------------------------------------------------- */
-#define NSLOTS 28
+#define NSLOTS 32
 static const char *g_slot_names[NSLOTS] = {
     "allreduce", "reduce_scatter", "allgather", "bcast", "reduce_local", "reduce", "reduce_scatter_block", "scan",
     "exscan",
@@ -361,9 +361,12 @@ static const char *g_slot_names[NSLOTS] = {
     "allreduce_init", "reduce_init", "reduce_scatter_init", "reduce_scatter_block_init", "scan_init", "exscan_init",
     "allgather_init", "bcast_init",
     /* exchanges (coll.h:204-219), appended: the indices above stay */
-    "alltoall", "alltoallv", "allgatherv"};
+    "alltoall", "alltoallv", "allgatherv",
+    /* rooted exchanges (coll.h:231-258), appended likewise */
+    "gather", "gatherv", "scatter", "scatterv"};
 enum { S_IALLREDUCE = 9, S_IREDUCE, S_IREDUCE_SCATTER, S_IREDUCE_SCATTER_BLOCK, S_ISCAN, S_IEXSCAN, S_IALLGATHER,
-       S_IBCAST, S_PERSISTENT0, S_ALLTOALL = 25, S_ALLTOALLV, S_ALLGATHERV };
+       S_IBCAST, S_PERSISTENT0, S_ALLTOALL = 25, S_ALLTOALLV, S_ALLGATHERV, S_GATHER, S_GATHERV, S_SCATTER,
+       S_SCATTERV };
 
 struct ompi_communicator_t {
     int rank, size;
@@ -909,6 +912,111 @@ static int base_allgatherv(const void *sbuf, int scount, struct ompi_datatype_t 
     return OMPI_SUCCESS;
 }
 
+/* rooted exchanges, linear as coll/basic's (coll_basic_gather.c, coll_basic_scatter.c):
+ * the root receives or sends one block per peer.  On gather(): every rank
+ * contributes its packed block padded to the longest (a scatter: the root its
+ * packed row), and only the root (a scatter: every rank) takes blocks out.
+ * What is significant on the root only is read on the root only. */
+static int base_gatherv(const void *sbuf, int scount, struct ompi_datatype_t *sdt, void *rbuf, const int *rcounts,
+                        const int *disps, struct ompi_datatype_t *rdt, int root, struct ompi_communicator_t *c,
+                        mca_coll_base_module_t *m)
+{
+    (void)m;
+    const int n = c->size, inplace = sbuf == MPI_IN_PLACE;
+    size_t mine_b = inplace ? 0 : (size_t)scount * sdt->size, maxb = 0;
+    size_t *B = (size_t *)gather(c, &mine_b, sizeof mine_b);
+    if (!B) return OMPI_ERROR;
+    for (int p = 0; p < n; p++)
+        if (B[p] > maxb) maxb = B[p];
+    if (!maxb) { free(B); return OMPI_SUCCESS; }
+    char *mine = calloc(1, maxb + 1), *all;
+    if (!mine) { free(B); return OMPI_ERR_OUT_OF_RESOURCE; }
+    if (mine_b) dtype_pack(sdt, scount, sbuf, mine);
+    all = gather(c, mine, maxb);
+    free(mine);
+    if (!all) { free(B); return OMPI_ERROR; }
+    if (c->rank == root)
+        for (int p = 0; p < n; p++) {
+            size_t len = B[p];
+            if (p == root && inplace) continue;   /* the root's block is where it belongs */
+            if (len > (size_t)rcounts[p] * rdt->size) len = (size_t)rcounts[p] * rdt->size;   /* never past the receive count */
+            dtype_unpack(rdt, (int)(len / rdt->size), all + (size_t)p * maxb,
+                         (char *)rbuf + (size_t)disps[p] * dtype_extent(rdt));
+        }
+    free(all);
+    free(B);
+    return OMPI_SUCCESS;
+}
+
+static int base_scatterv(const void *sbuf, const int *scounts, const int *disps, struct ompi_datatype_t *sdt,
+                         void *rbuf, int rcount, struct ompi_datatype_t *rdt, int root, struct ompi_communicator_t *c,
+                         mca_coll_base_module_t *m)
+{
+    (void)m;
+    const int n = c->size, is_root = c->rank == root;
+    size_t *row = calloc((size_t)n, sizeof *row), *B, total = 0, off = 0;
+    if (!row) return OMPI_ERR_OUT_OF_RESOURCE;
+    if (is_root)
+        for (int q = 0; q < n; q++) row[q] = (size_t)scounts[q] * sdt->size;
+    B = (size_t *)gather(c, row, (size_t)n * sizeof *row);   /* the root's row of sizes reaches every rank */
+    free(row);
+    if (!B) return OMPI_ERROR;
+    const size_t *R = B + (size_t)root * n;
+    for (int q = 0; q < n; q++) total += R[q];
+    for (int q = 0; q < c->rank; q++) off += R[q];
+    if (!total) { free(B); return OMPI_SUCCESS; }
+    char *mine = calloc(1, total + 1), *all;
+    if (!mine) { free(B); return OMPI_ERR_OUT_OF_RESOURCE; }
+    if (is_root) {
+        size_t o = 0;
+        for (int q = 0; q < n; q++) {
+            dtype_pack(sdt, scounts[q], (const char *)sbuf + (size_t)disps[q] * dtype_extent(sdt), mine + o);
+            o += R[q];
+        }
+    }
+    all = gather(c, mine, total);
+    free(mine);
+    if (!all) { free(B); return OMPI_ERROR; }
+    if (rbuf != MPI_IN_PLACE) {   /* in place (the root only): its block stays */
+        size_t len = R[c->rank];
+        if (len > (size_t)rcount * rdt->size) len = (size_t)rcount * rdt->size;   /* never past the receive count */
+        dtype_unpack(rdt, (int)(len / rdt->size), all + (size_t)root * total + off, rbuf);
+    }
+    free(all);
+    free(B);
+    return OMPI_SUCCESS;
+}
+
+/* rank p's block at p x count: the tables of the v-forms (read on the root only) */
+static int even_tables(int n, int count, int **counts, int **disps)
+{
+    *counts = calloc((size_t)n, sizeof **counts);
+    *disps = calloc((size_t)n, sizeof **disps);
+    if (!*counts || !*disps) { free(*counts); free(*disps); return OMPI_ERR_OUT_OF_RESOURCE; }
+    for (int p = 0; p < n; p++) { (*counts)[p] = count; (*disps)[p] = p * count; }
+    return OMPI_SUCCESS;
+}
+static int base_gather(const void *sbuf, int scount, struct ompi_datatype_t *sdt, void *rbuf, int rcount,
+                       struct ompi_datatype_t *rdt, int root, struct ompi_communicator_t *c, mca_coll_base_module_t *m)
+{
+    int *counts, *disps, rc = even_tables(c->size, c->rank == root ? rcount : 0, &counts, &disps);
+    if (rc) return rc;
+    rc = base_gatherv(sbuf, scount, sdt, rbuf, counts, disps, rdt, root, c, m);
+    free(counts);
+    free(disps);
+    return rc;
+}
+static int base_scatter(const void *sbuf, int scount, struct ompi_datatype_t *sdt, void *rbuf, int rcount,
+                        struct ompi_datatype_t *rdt, int root, struct ompi_communicator_t *c, mca_coll_base_module_t *m)
+{
+    int *counts, *disps, rc = even_tables(c->size, c->rank == root ? scount : 0, &counts, &disps);
+    if (rc) return rc;
+    rc = base_scatterv(sbuf, counts, disps, sdt, rbuf, rcount, rdt, root, c, m);
+    free(counts);
+    free(disps);
+    return rc;
+}
+
 /* coll/self-like reduce_local: mca_coll_base_reduce_local (coll_base_reduce.c:42-49) */
 static int base_reduce_local(const void *in, void *inout, int count, struct ompi_datatype_t *dt, struct ompi_op_t *op,
                              mca_coll_base_module_t *m)
@@ -986,6 +1094,35 @@ static int self_allgatherv(const void *sbuf, int scount, struct ompi_datatype_t 
 {
     (void)c; (void)m;
     return self_copy(sbuf, sdt, scount, (char *)rbuf + (size_t)disps[0] * dtype_extent(rdt), rdt, rcounts[0]);
+}
+static int self_gather(const void *sbuf, int scount, struct ompi_datatype_t *sdt, void *rbuf, int rcount,
+                       struct ompi_datatype_t *rdt, int root, struct ompi_communicator_t *c, mca_coll_base_module_t *m)
+{
+    (void)root; (void)c; (void)m;
+    return self_copy(sbuf, sdt, scount, rbuf, rdt, rcount);
+}
+static int self_gatherv(const void *sbuf, int scount, struct ompi_datatype_t *sdt, void *rbuf, const int *rcounts,
+                        const int *disps, struct ompi_datatype_t *rdt, int root, struct ompi_communicator_t *c,
+                        mca_coll_base_module_t *m)
+{
+    (void)root; (void)c; (void)m;
+    if (sbuf == MPI_IN_PLACE) return self_copy(sbuf, rdt, 0, rbuf, rdt, 0);
+    return self_copy(sbuf, sdt, scount, (char *)rbuf + (size_t)disps[0] * dtype_extent(rdt), rdt, rcounts[0]);
+}
+static int self_scatter(const void *sbuf, int scount, struct ompi_datatype_t *sdt, void *rbuf, int rcount,
+                        struct ompi_datatype_t *rdt, int root, struct ompi_communicator_t *c, mca_coll_base_module_t *m)
+{
+    (void)root; (void)c; (void)m;
+    if (rbuf == MPI_IN_PLACE) return self_copy(MPI_IN_PLACE, sdt, 0, rbuf, sdt, 0);
+    return self_copy(sbuf, sdt, scount, rbuf, rdt, rcount);
+}
+static int self_scatterv(const void *sbuf, const int *scounts, const int *disps, struct ompi_datatype_t *sdt,
+                         void *rbuf, int rcount, struct ompi_datatype_t *rdt, int root, struct ompi_communicator_t *c,
+                         mca_coll_base_module_t *m)
+{
+    (void)root; (void)c; (void)m;
+    if (rbuf == MPI_IN_PLACE) return self_copy(MPI_IN_PLACE, sdt, 0, rbuf, sdt, 0);
+    return self_copy((const char *)sbuf + (size_t)disps[0] * dtype_extent(sdt), sdt, scounts[0], rbuf, rdt, rcount);
 }
 static int self_bcast(void *buf, int count, struct ompi_datatype_t *dt, int root, struct ompi_communicator_t *c,
                       mca_coll_base_module_t *m)
@@ -1426,7 +1563,9 @@ static int comm_select(struct ompi_communicator_t *c, int is_self)
                             (void *)(MOD)->coll_scan_init, (void *)(MOD)->coll_exscan_init,          \
                             (void *)(MOD)->coll_allgather_init, (void *)(MOD)->coll_bcast_init,      \
                             (void *)(MOD)->coll_alltoall, (void *)(MOD)->coll_alltoallv,             \
-                            (void *)(MOD)->coll_allgatherv};                                         \
+                            (void *)(MOD)->coll_allgatherv, (void *)(MOD)->coll_gather,              \
+                            (void *)(MOD)->coll_gatherv, (void *)(MOD)->coll_scatter,                \
+                            (void *)(MOD)->coll_scatterv};                                           \
         for (int i_ = 0; i_ < NSLOTS; i_++)                                                          \
             if (f_[i_]) { c->fn[i_] = f_[i_]; c->mod[i_] = (MOD); c->owner[i_] = (OWNER); }          \
     } while (0)
@@ -1446,6 +1585,10 @@ static int comm_select(struct ompi_communicator_t *c, int is_self)
         b->coll_alltoall = self_alltoall;
         b->coll_alltoallv = self_alltoallv;
         b->coll_allgatherv = self_allgatherv;
+        b->coll_gather = self_gather;
+        b->coll_gatherv = self_gatherv;
+        b->coll_scatter = self_scatter;
+        b->coll_scatterv = self_scatterv;
         COPY(b, "self");
         base_prio = 75;
     } else {
@@ -1465,6 +1608,10 @@ static int comm_select(struct ompi_communicator_t *c, int is_self)
         b->coll_alltoall = base_alltoall;
         b->coll_alltoallv = base_alltoallv;
         b->coll_allgatherv = base_allgatherv;
+        b->coll_gather = base_gather;
+        b->coll_gatherv = base_gatherv;
+        b->coll_scatter = base_scatter;
+        b->coll_scatterv = base_scatterv;
         if (!coll_excluded("basic")) COPY(b, "basic");
         /* libnbc (10): the nonblocking and persistent slots */
         b = &g_libnbc_coll;
@@ -1493,6 +1640,10 @@ static int comm_select(struct ompi_communicator_t *c, int is_self)
         b->coll_alltoall = base_alltoall;
         b->coll_alltoallv = base_alltoallv;
         b->coll_allgatherv = base_allgatherv;
+        b->coll_gather = base_gather;
+        b->coll_gatherv = base_gatherv;
+        b->coll_scatter = base_scatter;
+        b->coll_scatterv = base_scatterv;
         {
             int fan;
             if (tuned_forced("scan", &fan)) b->coll_scan = tuned_scan;
@@ -1726,6 +1877,36 @@ int mxh_allgatherv(const void *sbuf, int scount, void *sdt, void *rbuf, const in
     struct ompi_communicator_t *c = cv;
     return ((mca_coll_base_module_allgatherv_fn_t)c->fn[S_ALLGATHERV])(sbuf, scount, sdt, rbuf, rcounts, disps, rdt, c,
                                                                        c->mod[S_ALLGATHERV]);
+}
+
+int mxh_gather(const void *sbuf, int scount, void *sdt, void *rbuf, int rcount, void *rdt, int root, void *cv)
+{
+    struct ompi_communicator_t *c = cv;
+    return ((mca_coll_base_module_gather_fn_t)c->fn[S_GATHER])(sbuf, scount, sdt, rbuf, rcount, rdt, root, c,
+                                                               c->mod[S_GATHER]);
+}
+
+int mxh_gatherv(const void *sbuf, int scount, void *sdt, void *rbuf, const int *rcounts, const int *disps, void *rdt,
+                int root, void *cv)
+{
+    struct ompi_communicator_t *c = cv;
+    return ((mca_coll_base_module_gatherv_fn_t)c->fn[S_GATHERV])(sbuf, scount, sdt, rbuf, rcounts, disps, rdt, root, c,
+                                                                 c->mod[S_GATHERV]);
+}
+
+int mxh_scatter(const void *sbuf, int scount, void *sdt, void *rbuf, int rcount, void *rdt, int root, void *cv)
+{
+    struct ompi_communicator_t *c = cv;
+    return ((mca_coll_base_module_scatter_fn_t)c->fn[S_SCATTER])(sbuf, scount, sdt, rbuf, rcount, rdt, root, c,
+                                                                 c->mod[S_SCATTER]);
+}
+
+int mxh_scatterv(const void *sbuf, const int *scounts, const int *disps, void *sdt, void *rbuf, int rcount, void *rdt,
+                 int root, void *cv)
+{
+    struct ompi_communicator_t *c = cv;
+    return ((mca_coll_base_module_scatterv_fn_t)c->fn[S_SCATTERV])(sbuf, scounts, disps, sdt, rbuf, rcount, rdt, root, c,
+                                                                   c->mod[S_SCATTERV]);
 }
 
 int mxh_bcast(void *buf, int count, void *dt, int root, void *cv)

@@ -106,6 +106,15 @@ int mxh_alltoallv(const void *sbuf, const int *scounts, const int *sdispls, void
                   const int *rcounts, const int *rdispls, void *rdtype, void *comm);
 int mxh_allgatherv(const void *sbuf, int scount, void *sdtype, void *rbuf, const int *rcounts, const int *displs,
                    void *rdtype, void *comm);
+/* MPI_Gather / MPI_Gatherv / MPI_Scatter / MPI_Scatterv: the receive arguments
+ * of the gathers and the send arguments of the scatters are read on the root
+ * only; MPI_IN_PLACE (1) as sbuf of a gather's root, as rbuf of a scatter's */
+int mxh_gather(const void *sbuf, int scount, void *sdtype, void *rbuf, int rcount, void *rdtype, int root, void *comm);
+int mxh_gatherv(const void *sbuf, int scount, void *sdtype, void *rbuf, const int *rcounts, const int *displs,
+                void *rdtype, int root, void *comm);
+int mxh_scatter(const void *sbuf, int scount, void *sdtype, void *rbuf, int rcount, void *rdtype, int root, void *comm);
+int mxh_scatterv(const void *sbuf, const int *scounts, const int *displs, void *sdtype, void *rbuf, int rcount,
+                 void *rdtype, int root, void *comm);
 int mxh_bcast(void *buf, int count, void *dtype, int root, void *comm);
 int mxh_reduce(const void *sbuf, void *rbuf, int count, void *dtype, void *op, int root, void *comm);
 int mxh_reduce_scatter_block(const void *sbuf, void *rbuf, int rcount, void *dtype, void *op, void *comm);

@@ -205,6 +205,19 @@ typedef int (*mca_coll_base_module_scan_fn_t)(const void *sbuf, void *rbuf, int 
                                               struct ompi_op_t *op, struct ompi_communicator_t *comm,
                                               mca_coll_base_module_t *module);
 typedef mca_coll_base_module_scan_fn_t mca_coll_base_module_exscan_fn_t;
+/* rooted exchanges (coll.h:231-238, :251-258) */
+typedef int (*mca_coll_base_module_gather_fn_t)(const void *sbuf, int scount, struct ompi_datatype_t *sdtype,
+                                                void *rbuf, int rcount, struct ompi_datatype_t *rdtype, int root,
+                                                struct ompi_communicator_t *comm, mca_coll_base_module_t *module);
+typedef int (*mca_coll_base_module_gatherv_fn_t)(const void *sbuf, int scount, struct ompi_datatype_t *sdtype,
+                                                 void *rbuf, const int *rcounts, const int *disps,
+                                                 struct ompi_datatype_t *rdtype, int root,
+                                                 struct ompi_communicator_t *comm, mca_coll_base_module_t *module);
+typedef mca_coll_base_module_gather_fn_t mca_coll_base_module_scatter_fn_t;   /* the same argument list */
+typedef int (*mca_coll_base_module_scatterv_fn_t)(const void *sbuf, const int *scounts, const int *disps,
+                                                  struct ompi_datatype_t *sdtype, void *rbuf, int rcount,
+                                                  struct ompi_datatype_t *rdtype, int root,
+                                                  struct ompi_communicator_t *comm, mca_coll_base_module_t *module);
 /* nonblocking (coll.h:261-338) and persistent (:339-420: + MPI_Info) */
 #define MX_NB_ARGS struct ompi_communicator_t *comm, struct ompi_request_t **request, mca_coll_base_module_t *module
 #define MX_PI_ARGS struct ompi_communicator_t *comm, struct ompi_info_t *info, struct ompi_request_t **request, \
@@ -263,12 +276,14 @@ struct mca_coll_base_module_2_3_0_t {
     mx_coll_slot_unused_t coll_alltoallw, coll_barrier;
     mca_coll_base_module_bcast_fn_t coll_bcast;
     mca_coll_base_module_exscan_fn_t coll_exscan;
-    mx_coll_slot_unused_t coll_gather, coll_gatherv;
+    mca_coll_base_module_gather_fn_t coll_gather;
+    mca_coll_base_module_gatherv_fn_t coll_gatherv;
     mca_coll_base_module_reduce_fn_t coll_reduce;
     mca_coll_base_module_reduce_scatter_fn_t coll_reduce_scatter;
     mca_coll_base_module_reduce_scatter_block_fn_t coll_reduce_scatter_block;
     mca_coll_base_module_scan_fn_t coll_scan;
-    mx_coll_slot_unused_t coll_scatter, coll_scatterv;
+    mca_coll_base_module_scatter_fn_t coll_scatter;
+    mca_coll_base_module_scatterv_fn_t coll_scatterv;
     /* nonblocking (17) */
     mca_coll_base_module_iallgather_fn_t coll_iallgather;
     mx_coll_slot_unused_t coll_iallgatherv;

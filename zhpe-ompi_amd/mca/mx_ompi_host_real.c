@@ -147,6 +147,7 @@ static void *h_coll(struct ompi_communicator_t *c, const char *slot, struct mca_
     MX_SLOT(allreduce_init) MX_SLOT(reduce_init) MX_SLOT(reduce_scatter_init) MX_SLOT(reduce_scatter_block_init)
     MX_SLOT(scan_init) MX_SLOT(exscan_init) MX_SLOT(allgather_init) MX_SLOT(bcast_init)
     MX_SLOT(alltoall) MX_SLOT(alltoallv) MX_SLOT(allgatherv)
+    MX_SLOT(gather) MX_SLOT(gatherv) MX_SLOT(scatter) MX_SLOT(scatterv)
 #undef MX_SLOT
     *m = NULL;
     return NULL;

@@ -325,6 +325,17 @@ def _coll_lib():
         L.mx_exchange_vec_geometry.argtypes = [ctypes.c_uint, szp, szp]
         L.mx_exchange_vec_widths.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
         L.mx_ddt_strided.argtypes = [vp, i]
+        L.mx_gather.argtypes = [vp, vp, sz, vp, vp, sz, vp, i, vp]
+        L.mx_scatter.argtypes = [vp, vp, sz, vp, vp, sz, vp, i, vp]
+        L.mx_gatherv.argtypes = [vp, vp, sz, vp, vp, szp, i64p, vp, i, vp]
+        L.mx_scatterv.argtypes = [vp, vp, szp, i64p, vp, vp, sz, vp, i, vp]
+        L.mx_gather_local.argtypes = [vp, pp, sz, vp, pp, sz, vp, i, vp]
+        L.mx_scatter_local.argtypes = [vp, pp, sz, vp, pp, sz, vp, i, vp]
+        L.mx_gatherv_local.argtypes = [vp, pp, szp, vp, pp, szp, i64p, vp, i, vp]
+        L.mx_scatterv_local.argtypes = [vp, pp, szp, i64p, vp, pp, szp, vp, i, vp]
+        L.mx_comm_rooted_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
+        L.mx_comm_rooted_rounds.argtypes = [vp, i, sz]
+        L.mx_comm_rooted_rounds.restype = ctypes.c_longlong
         L.mx_bcast_local.argtypes = [vp, pp, sz, i, vp]
         L.mx_allreduce_decision.argtypes = [i, sz, i]
         L.mx_comm_set_profiling.argtypes = [vp, i]
@@ -549,6 +560,14 @@ def exchange_ddt_stats_total():
     return dict(zip(_XD_KEYS, (int(v) for v in out)))
 
 
+def rooted_stats_total():
+    """Rooted exchange calls (gather, gatherv, scatter, scatterv) of every
+    communicator of this process (mx_comm_rooted_stats with a null communicator)."""
+    out = (ctypes.c_uint64 * 4)()
+    check(_coll_lib().mx_comm_rooted_stats(None, out), "mx_comm_rooted_stats")
+    return dict(zip(_XD_KEYS, (int(v) for v in out)))
+
+
 def exchange_tables_live():
     """Table memories of the exchange kernel alive in this process (a test hook)."""
     return _coll_lib().mx_exchange_tables_live()
@@ -733,6 +752,40 @@ class Comm:
         check(min(rc, 0), "mx_comm_exchange_rounds")
         return rc
 
+    # rooted exchanges: a datatype None = bytes (counts in bytes, displacements
+    # byte offsets), else instances and extents; the many-block side is read on
+    # the root only (None elsewhere); in place at the root: sbuf (gathers) or
+    # rbuf (scatters) IN_PLACE
+    def gather(self, sbuf, scount, sddt, rbuf, rcount, rddt, root, stream=0):
+        check(_coll_lib().mx_gather(self.h, sbuf, scount, _ddt_h(sddt), rbuf, rcount, _ddt_h(rddt), root,
+                                    stream or None), "mx_gather")
+
+    def gatherv(self, sbuf, scount, sddt, rbuf, rcounts, rdispls, rddt, root, stream=0):
+        check(_coll_lib().mx_gatherv(self.h, sbuf, scount, _ddt_h(sddt), rbuf, _sizes(rcounts), _i64s(rdispls),
+                                     _ddt_h(rddt), root, stream or None), "mx_gatherv")
+
+    def scatter(self, sbuf, scount, sddt, rbuf, rcount, rddt, root, stream=0):
+        check(_coll_lib().mx_scatter(self.h, sbuf, scount, _ddt_h(sddt), rbuf, rcount, _ddt_h(rddt), root,
+                                     stream or None), "mx_scatter")
+
+    def scatterv(self, sbuf, scounts, sdispls, sddt, rbuf, rcount, rddt, root, stream=0):
+        check(_coll_lib().mx_scatterv(self.h, sbuf, _sizes(scounts), _i64s(sdispls), _ddt_h(sddt), rbuf, rcount,
+                                      _ddt_h(rddt), root, stream or None), "mx_scatterv")
+
+    def rooted_stats(self):
+        """Rooted exchange calls of this communicator (mx_comm_rooted_stats):
+        all, zero-copy, staged, and the staging rounds the staged ones took."""
+        out = (ctypes.c_uint64 * 4)()
+        check(_coll_lib().mx_comm_rooted_stats(self.h, out), "mx_comm_rooted_stats")
+        return dict(zip(_XD_KEYS, (int(v) for v in out)))
+
+    def rooted_rounds(self, scatter, max_block):
+        """Staging rounds of a staged gather (scatter false) or scatter whose
+        largest block is max_block bytes."""
+        rc = _coll_lib().mx_comm_rooted_rounds(self.h, 1 if scatter else 0, max_block)
+        check(min(rc, 0), "mx_comm_rooted_rounds")
+        return rc
+
     def shmem_reduce(self, op, t, dt_size, target, source, nreduce, stream=0):
         """shmem_<t>_<op>_to_all over this communicator's ranks (scoll/mpi path)."""
         sops = ["AND", "OR", "XOR", "MAX", "MIN", "SUM", "PROD"]
@@ -878,6 +931,27 @@ class Comm:
         sp = _ptrs(sbufs) if sbufs is not None else None
         check(_coll_lib().mx_allgatherv_local(self.h, sp, _ptrs(rbufs), _sizes(rbytes), _sizes(roffs),
                                               stream or None), "mx_allgatherv_local")
+
+    # rooted exchanges on a local communicator: `size` buffers a side (only the
+    # root's entry of the many-block side is read); the v-forms take one count
+    # per rank on the other side
+    def gather_local(self, sbufs, scount, sddt, rbufs, rcount, rddt, root, stream=0):
+        check(_coll_lib().mx_gather_local(self.h, _ptrs(sbufs), scount, _ddt_h(sddt), _ptrs(rbufs), rcount,
+                                          _ddt_h(rddt), root, stream or None), "mx_gather_local")
+
+    def gatherv_local(self, sbufs, scounts, sddt, rbufs, rcounts, rdispls, rddt, root, stream=0):
+        check(_coll_lib().mx_gatherv_local(self.h, _ptrs(sbufs), _sizes(scounts), _ddt_h(sddt), _ptrs(rbufs),
+                                           _sizes(rcounts), _i64s(rdispls), _ddt_h(rddt), root, stream or None),
+              "mx_gatherv_local")
+
+    def scatter_local(self, sbufs, scount, sddt, rbufs, rcount, rddt, root, stream=0):
+        check(_coll_lib().mx_scatter_local(self.h, _ptrs(sbufs), scount, _ddt_h(sddt), _ptrs(rbufs), rcount,
+                                           _ddt_h(rddt), root, stream or None), "mx_scatter_local")
+
+    def scatterv_local(self, sbufs, scounts, sdispls, sddt, rbufs, rcounts, rddt, root, stream=0):
+        check(_coll_lib().mx_scatterv_local(self.h, _ptrs(sbufs), _sizes(scounts), _i64s(sdispls), _ddt_h(sddt),
+                                            _ptrs(rbufs), _sizes(rcounts), _ddt_h(rddt), root, stream or None),
+              "mx_scatterv_local")
 
     def bcast_local(self, bufs, nbytes, root, stream=0):
         check(_coll_lib().mx_bcast_local(self.h, _ptrs(bufs), nbytes, root, stream or None), "mx_bcast_local")
