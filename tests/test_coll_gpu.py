@@ -37,7 +37,12 @@ def _oracle():
 
 def gen(t, op, count, seed):
     """Adversarial inputs: magnitudes spanning 16 decades (so FP order
-    matters), NaN/-0 for MAX/MIN, ties for MAXLOC, 0/1 for bool."""
+    matters), NaN/-0 for MAX/MIN, ties for MAXLOC, 0/1 for bool.
+
+    Types not named below get raw random bytes.  New cases should take their
+    operands from op_values.edge_values, which knows every (op, type) pair
+    (tests/test_pair_matrix_gpu.py); this generator stays as it is for the
+    cases that already use it."""
     rng = np.random.default_rng(seed)
     es = mxompi.type_size(t)
     if t in ("FLOAT", "DOUBLE"):

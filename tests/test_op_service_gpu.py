@@ -29,6 +29,10 @@ SVC_SOLO = 64 << 10          # kSvcSoloBytes: above, the whole grid takes the co
 
 
 def _gen(op, t, count, seed):
+    """Operands of the pairs in PAIRS; other types get raw random bytes.
+    New cases should use op_values.edge_values, the generator for every
+    (op, type) pair (tests/test_pair_matrix_gpu.py runs them all through the
+    service)."""
     rng = np.random.default_rng(seed)
     es = mxompi.type_size(t)
     if t in ("FLOAT", "DOUBLE"):
