@@ -2385,6 +2385,9 @@ static int reduce_scatter_impl(mx_comm_t *c, const void *sbuf, void *rbuf, const
       for (int j = 0; j < n; j++) sp[j] = (j == r) ? sb + e0 * es : c->staging + (size_t)j * slot + mis;
       char *dst = overlap ? c->staging + (size_t)n * slot + mis : (char *)rbuf + k0 * es;
       char *dp[1] = {dst};
+      // padded types are stored field by field: the spare slot starts as the
+      // bytes the result replaces, so the copy back keeps rbuf's padding
+      if (overlap && (rc = copy_async(dst, (char *)rbuf + k0 * es, kl * es, s))) return rc;
       for (const Seg &sg : segs) {
         const Seg piece{std::max(sg.lo, e0), std::min(sg.hi, e0 + kl), sg.p};
         if (piece.lo < piece.hi && (rc = run_fold(c, fl, piece, e0, sp, n, dp, 1, es, s))) return rc;
@@ -3554,6 +3557,9 @@ static int vm_scatter_blocks(mx_comm *c, vm_launch_fn vl, const VmProg &p, const
       a.dst[r] = dst;
       a.n = kl;
       a.p = p;
+      // the fold stores the fields of an element only: the spare slot starts
+      // as the bytes the result replaces, so the copy back keeps rbuf's padding
+      if (overlap && (rc = copy_async(dst, rb + k0 * es, kl * es, s))) return rc;
       prof_begin(c, s);
       if ((rc = vl(a, s))) return rc;
       prof_end(c, s, 0, (double)(n + 1) * (double)kl * (double)es);
